@@ -1,6 +1,8 @@
 """bench.py — MoCo-v2 ResNet-50 two-view training step on N MI355X GPUs (one process per GPU).
 
     python bench.py                                   # N=1, 50 timed steps after 5 warm-up steps
+    python bench.py --full                            # + roofline loop, CPU baseline, HBM-traffic figures
+    python bench.py --dump-outputs DIR                # + what the last timed step computed, as DIR/<name>.npy
     python bench.py --gpus 8                          # spawns 8 ranks itself (torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8 --steps 50 --warmup 5       # the driver's form
@@ -10,13 +12,20 @@ q forward (train BN), key-encoder EMA, k forward, fused InfoNCE, enqueue, backwa
 all-reduce (N>1), momentum-SGD, lr step — driven through the Trainer's whole hook bus
 (train_iter_begin / train_iter_end of OptimizerHook, IterTimerHook, LogHook, LRSchedulerHook, ...).
 
-Two loops:
+A plain run sets up, warms up and times:
   1. the TIMED loop: exactly --steps steps, nothing but the product path between a barrier +
-     torch.cuda.synchronize() on both sides -> `value`, `ms_per_step`;
-  2. an INSTRUMENTED loop afterwards (HIP events around every launch of the three MFMA kernels on
+     torch.cuda.synchronize() on both sides -> `value`, `ms_per_step`.
+With --full, after it:
+  2. an INSTRUMENTED loop (HIP events around every launch of the three MFMA kernels on
      their launch stream; the library sums each launch's algorithmic FLOPs / bytes from its
      descriptor) -> `roofline` (the dominant kernel) + the two next ones.  It never contributes to
-     `value`.
+     `value`;
+  3. the HBM-traffic floor of the step from the committed PMC summary (`hbm`), the exposed part of the
+     gradient all-reduce (N > 1: 3 extra steps) and the CPU oracle baseline (`cpu_baseline`).
+--dump-outputs DIR writes what the last timed step computed (rank 0): every tensor the step returns and a fixed
+sample of the model's state after it (parameters, running statistics, MoCo's queue), as float32 / float64 .npy
+files, under 64 MB in all.  The inputs (synthetic batch, initial weights: seeded here) are the same for the same
+arguments.
 Prints ONE JSON line (rank 0).  `value` = images/s over all ranks, where one image = one two-view
 sample (PASSL's own `ips`, passl/engine/loops/loop.py:102-104).
 """
@@ -110,7 +119,13 @@ def parse():
                          'inputs: a ring of RING (>= 3) pinned host batches, each copied host -> device one step ahead '
                          'on a copy stream (datasets/synthetic.py:HostRingLoader) -> value_fresh_inputs')
     ap.add_argument('--roofline-steps', type=int, default=10,
-                    help='steps of the instrumented loop that follows the timed loop')
+                    help='steps of the instrumented loop that follows the timed loop (--full)')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline figure, also measure what takes runs of its own: the instrumented '
+                         'roofline loop, the exposed gradient all-reduce (N > 1), the HBM-traffic floor of the '
+                         'committed PMC passes and the CPU baseline (off by default: a plain run only times the steps)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write what the last timed step computed as DIR/<name>.npy (float32 / float64, < 64 MB)')
     return ap.parse_args()
 
 
@@ -176,6 +191,46 @@ def pmc_traffic(args):
     if 'fetch_gb_per_step' in z and 'write_gb_per_step' in z:
         out['_step'] = {'fetch_gb': z['fetch_gb_per_step'], 'write_gb': z['write_gb_per_step'], 'source': src}
     return out
+
+
+DUMP_SAMPLE = 16384            # elements kept of a larger state tensor (--dump-outputs)
+
+
+def dump_outputs(trainer, out_dir):
+    """--dump-outputs: the tensors the last step returned (trainer.outputs) in full, and the model's state after that
+    step (parameters and buffers: running statistics, MoCo's queue), a tensor of more than DUMP_SAMPLE elements as a
+    fixed sample of its flattened values (indices drawn from a generator seeded by the tensor's name, sorted; the
+    indices go to <name>.idx.npy).  float32, integer tensors float64.  -> (files, bytes)"""
+    import zlib
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    files, nbytes = 0, 0
+
+    def save(name, t, sample):
+        nonlocal files, nbytes
+        t = t.detach().reshape(-1) if sample else t.detach()
+        if sample and t.numel() > DUMP_SAMPLE:
+            gen = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=gen).sort().values
+            np.save(os.path.join(out_dir, name + '.idx.npy'), idx.double().numpy())
+            nbytes += DUMP_SAMPLE * 8
+            t = t[idx.to(t.device)]
+        a = t.cpu()
+        a = a.double() if not (a.is_floating_point() or a.is_complex()) else a.float()
+        np.save(os.path.join(out_dir, name + '.npy'), a.numpy())
+        files, nbytes = files + 1, nbytes + a.numel() * a.element_size()
+
+    for k, v in sorted((trainer.outputs or {}).items()):
+        if torch.is_tensor(v):
+            save('out.' + k, v, sample=False)
+    model = trainer.model.module if hasattr(trainer.model, 'module') else trainer.model
+    for k, v in model.state_dict().items():
+        if torch.is_tensor(v) and v.numel() > 0:
+            save('state.' + k, v, sample=True)
+    assert nbytes < 64 * 2 ** 20, 'bench.py --dump-outputs: %d bytes' % nbytes
+    return files, nbytes
 
 
 def pin_rank_to_cores():
@@ -280,6 +335,15 @@ def main():
         cfg.hip_graph = True
     if args.eager:
         cfg.step_plan = False
+    # the same arguments give the same inputs: the Trainer seeds only a non-zero config seed (the synthetic batch has
+    # its own generator), and torch's default generator otherwise starts from a fresh seed in every process, so the
+    # initial weights and MoCo's initial queue would differ from run to run
+    import random
+    import numpy as np
+    seed = int(cfg.get('seed', 0) or 0) + rank
+    torch.manual_seed(seed)
+    np.random.seed(seed)
+    random.seed(seed)
     trainer = Trainer(cfg)
     trainer.mode = 'train'
     trainer.model.train()
@@ -335,6 +399,8 @@ def main():
     host_elapsed = time.perf_counter() - t0          # the host is done enqueueing; the GPU may still be running
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(trainer, args.dump_outputs)
     loss = float(trainer.outputs['loss'].detach())
     mem = torch.cuda.memory_stats()
     launch_desc = step_launch(trainer)      # how the TIMED steps were issued (the instrumentation below may drop the plan)
@@ -377,7 +443,7 @@ def main():
     # the launches' algorithmic FLOPs / bytes itself.  The side stream is off here so that a kernel's
     # duration is its own (in the timed loop the weight gradients run next to the main chain).
     kern, rsteps, instr_elapsed, event_overhead_us = {}, 0, 0.0, 0.0
-    if not args.no_kernel_timing and args.roofline_steps > 0:
+    if args.full and not args.no_kernel_timing and args.roofline_steps > 0:
         import ctypes
         from passl_amd.hip import config as hip_config
         lib = L.load()
@@ -428,7 +494,7 @@ def main():
         exposed = None
         red = getattr(trainer, 'grad_reducer', None)
         host_ms = None
-        if red is not None:
+        if red is not None and args.full:
             red.measure = True
             for r_ in getattr(red, 'reducers', [red]):
                 r_.host_ms, r_.host_calls = 0.0, 0
@@ -467,8 +533,8 @@ def main():
                        'hbm_allocated_gb': round(mem.get('allocated_bytes.all.peak', 0) / 2 ** 30, 1),
                        'hbm_reserved_gb': round(mem.get('reserved_bytes.all.peak', 0) / 2 ** 30, 1),
                        'allocator_retries': int(mem.get('num_alloc_retries', 0)),
-                       'timed_region': 'product path only (full hook bus); kernel instrumentation runs '
-                                       'in a separate loop afterwards',
+                       'timed_region': 'product path only (full hook bus); kernel instrumentation (--full) '
+                                       'runs in a separate loop afterwards',
                        'host_enqueue_ms_per_step': round(1000 * host_elapsed / args.steps, 3),
                        'step_launch': launch_desc, 'extra_untimed_steps': extra_warm,
                        'main_stream_priority': main_stream.priority if main_stream is not None else None},
@@ -477,7 +543,7 @@ def main():
                 'achieved_tflops_per_gpu': round(ips / world * flop_per_sample / 1e12, 2),
                 'frac_of_peak': round(ips / world * flop_per_sample / 1e12 / peak, 5)},
         }
-        step_traffic = (pmc_traffic(args) or {}).get('_step')
+        step_traffic = (pmc_traffic(args) or {}).get('_step') if args.full else None
         if step_traffic is not None:
             # the whole step against what its HBM traffic alone would cost (round-4 verdict: put the "x times its
             # traffic floor" claim into the record): counter bytes of the committed PMC passes of this command over
@@ -574,7 +640,7 @@ def main():
         if dist_info is not None:
             dist_info['rank0_cores'] = ('%d-%d' % (pinned[0], pinned[-1])) if pinned else None
             out['dist'] = dist_info
-        if world == 1 and not args.no_cpu_baseline and args.workload == 'moco':
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == 'moco':
             out['cpu_baseline'] = cpu_baseline()
         json_out.write(json.dumps(out) + '\n')
         json_out.flush()

@@ -137,11 +137,11 @@ def test_bench_self_launch_gpus1_and_world1_launcher():
     the production gate is world > 1) and the plain form; both print exactly one JSON line."""
     import json
     for cmd in ([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1',
-                 '--batch', '32', '--no-cpu-baseline', '--roofline-steps', '1'],
+                 '--batch', '32', '--full', '--no-cpu-baseline', '--roofline-steps', '1'],
                 [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1',
                  '--master-addr', '127.0.0.1', '--master-port', str(_free_port()),
                  os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1', '--batch', '32',
-                 '--no-cpu-baseline', '--roofline-steps', '1']):
+                 '--full', '--no-cpu-baseline', '--roofline-steps', '1']):
         r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0'),
                            capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
@@ -159,7 +159,7 @@ def test_bench_two_ranks_one_gpu_reports_its_ranks():
     import json
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
            '--master-addr', '127.0.0.1', '--master-port', str(_free_port()), os.path.join(ROOT, 'bench.py'),
-           '--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '16', '--no-cpu-baseline',
+           '--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '16', '--full', '--no-cpu-baseline',
            '--roofline-steps', '0', '--dp-buckets', '3']
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0', PASSL_DIST_BACKEND='gloo', PASSL_DEVICE_INDEX='0')
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)

@@ -108,25 +108,34 @@ class Report:
 def _oracle_run(geometry, N, hw, seed):
     """One training-mode forward + backward of the bf16-emulating encoder on the CPU, every stored tensor kept.
     moco_cfg2: MoCo-v2's query trunk (stem max-pool, kaiming init); simclr: SimCLR's pool-free trunk (Xavier init)
-    and its projector (NonLinearNeckfc3)."""
+    and its projector (NonLinearNeckfc3).
+    The convolutions and Linears accumulate in fp64 (oracle/resnet50.py ACCUM64, a valid evaluation of the same bf16
+    contract): an fp32 CPU convolution sums in an order that depends on the host's thread count, and through 50
+    layers of bf16 rounding and batch statistics that changes every recorded tensor; the fp64 sums make the
+    recording the same on every host."""
     gen = torch.Generator().manual_seed(seed + 100)
     img = torch.randn(N, 3, hw, hw, generator=gen)
     rec, new_stats = {}, {}
-    if geometry == 'moco_cfg2':
-        oracle = MoCoOracle(K=256, seed=seed, bf16=True)
-        st = oracle.q
-        for n in R.trainable_keys(st):
-            st[n] = st[n].detach().requires_grad_(True)
-        y = R.trunk_forward(st, img, False, new_stats, None, maxpool=True, bf16=True, rec=rec)
-    else:
-        oracle = S.SimCLROracle(seed=seed, bf16=True)
-        st = oracle.st
-        for n in R.trainable_keys(st):
-            st[n] = st[n].detach().requires_grad_(True)
-        y = S.encoder_forward(st, img, new_stats, None, bf16=True, rec=rec)
-    # any well-conditioned scalar: a fixed random projection of the output (gradients of every sign and size)
-    proj = torch.randn(y.shape, generator=gen)
-    (y * proj).sum().backward()
+    accum64 = R.ACCUM64
+    R.ACCUM64 = True
+    try:
+        if geometry == 'moco_cfg2':
+            oracle = MoCoOracle(K=256, seed=seed, bf16=True)
+            st = oracle.q
+            for n in R.trainable_keys(st):
+                st[n] = st[n].detach().requires_grad_(True)
+            y = R.trunk_forward(st, img, False, new_stats, None, maxpool=True, bf16=True, rec=rec)
+        else:
+            oracle = S.SimCLROracle(seed=seed, bf16=True)
+            st = oracle.st
+            for n in R.trainable_keys(st):
+                st[n] = st[n].detach().requires_grad_(True)
+            y = S.encoder_forward(st, img, new_stats, None, bf16=True, rec=rec)
+        # any well-conditioned scalar: a fixed random projection of the output (gradients of every sign and size)
+        proj = torch.randn(y.shape, generator=gen)
+        (y * proj).sum().backward()
+    finally:
+        R.ACCUM64 = accum64
     return oracle, st, new_stats, rec, img
 
 
@@ -282,13 +291,16 @@ def test_r50_layers_teacher_forced_bf16(geometry):
                 arena.clear_grad()
                 xh = _dev(rec['mlp.%d.x' % i_fc], requires_grad=True)
                 y = fc(xh, out_f32=True)
-                y.retain_grad()
-                z = bn(y, relu=relu)
+                # as in unit A: the BatchNorm1D sees the Linear's output as a leaf, and the Linear's backward gets
+                # the ORACLE's gradient (rounding it to bf16 the way the oracle does), not the product's
+                yl = y.detach().requires_grad_(True)
+                z = bn(yl, relu=relu)
                 rep.f32('neck mlp.%d (Linear, fp32 out) fwd' % i_fc, y, rec['mlp.%d.y' % i_fc], 1e-4)
                 rep.f32('neck mlp.%d (BatchNorm1D) fwd' % i_bn, z, rec['mlp.%d.z' % i_bn], 1e-3)
                 z.backward(rec['mlp.%d.z' % i_bn].grad.to(DEV))
+                y.backward(rec['mlp.%d.y' % i_fc].grad.to(DEV))
                 torch.cuda.synchronize()
-                rep.f32('neck mlp.%d bwd -> d(fc out)' % i_bn, y.grad, rec['mlp.%d.y' % i_fc].grad, 1e-3)
+                rep.f32('neck mlp.%d bwd -> d(fc out)' % i_bn, yl.grad, rec['mlp.%d.y' % i_fc].grad, 1e-3)
                 rep.bf16('neck mlp.%d dgrad' % i_fc, xh.grad, _grad_bf16(rec['mlp.%d.x' % i_fc]))
                 rep.f32('neck mlp.%d wgrad' % i_fc, fc.weight.grad, st['1.mlp.%d.weight' % i_fc].grad, 2e-3)
                 # (the Linear's bias feeds a batch-statistics BatchNorm: its gradient is mathematically zero, both

@@ -2,7 +2,7 @@
 summed per training step.  FETCH_SIZE is doubled: on gfx950 rocprofv3 tallies the 128-byte
 requests of wide coalesced reads at 64 B (MI355X_MICROARCH.md, HBM section); WRITE_SIZE is
 uncalibrated (reported as is).   python tools/pmc_summary.py <fetch.db> <write.db> <steps> [out.json]
-With out.json: per-kernel bytes per launch (the figure bench.py reports as roofline.traffic)."""
+With out.json: per-kernel bytes per launch (the figure `bench.py --full` reports as roofline.traffic)."""
 import re
 import sqlite3
 import sys
