@@ -41,38 +41,71 @@ enum passl_dtype { PASSL_F32 = 0, PASSL_BF16 = 1 };
 
 /* The value passl_hip_abi_version() of a library built from THIS header returns: a caller compiled against another
  * layout of the descriptors below must not call it (tools/kbench and passl_amd/hip/lib.py check at start-up). */
-#define PASSL_HIP_ABI_VERSION 15
+#define PASSL_HIP_ABI_VERSION 16
 int passl_hip_abi_version(void);
-/* Kernel-selection knobs (defaults are tuned for MI355X; tests use them to force a path):
- *   "igemm_ring" 0/1            use the LDS-DMA ring conv kernel when it applies (1)
- *   "igemm_ring_min_nk" n       ... only for reductions of at least n 64-element K-tiles (8)
- *   "igemm_ring_min_tiles" n    ... and launches with at least n output tiles (1)
- *   "igemm_ring_bm" 128|256     row-tile of the ring kernel: 128 (4 waves, 2 LDS stages, two
- *                               workgroups per CU; default) or 256 (8 waves, 3 stages, one)
- *   "igemm_8p" 0|1|2            the 256 x 256-tile 8-phase kernel: never / when its cost model prefers it to
- *                               the ring kernel (default) / whenever the launch is inside its envelope
- *   "igemm_8p_min_nk" n         ... (mode 1) only for reductions of at least n 64-element K-tiles (8)
- *   "igemm_8p_tk" / "_te" / "_ring_tk" / "_ring_te" / "_margin"   the cost model's constants (0.01 us per K-tile and
- *                               per tile of either kernel, margin in %: conv_igemm_8p.hip)
- *   "conv3x3_wave" 0/1          the wave-per-patch kernel (conv3x3_wave.hip) for 3x3 / stride 1 / pad 1 launches with 64 input
- *                               and 64 output channels whose image sides are multiples of 8 (ResNet-50 stage 1, forward and
- *                               data gradient; affine / ReLU, fused statistics or BatchNorm-backward epilogue): the nine weight
- *                               taps stay in LDS, every wave walks its own patches, no workgroup barrier (1);
- *                               "conv3x3_wave_rows" 4|8: 4 x 8 patches on eight waves (default) / 8 x 8 patches on four;
- *                               "conv3x3_wave_modes" bit mask of the launches that take it (1 plain / affine / ReLU, 2 fused
- *                               statistics, 4 BatchNorm-backward sums; default 7 — in-step experiments)
- *   "igemm_persist" 0/1         persistent form of the register-staged kernel for dense 1x1 launches: bit-identical, measured
- *                               slower (profiles/r06_negative_results.txt): off;  "igemm_persist_grid" n: its grid (tests)
- *   "wgrad_halo" 0|1|2          spatially tiled 3x3 / stride 1 weight-gradient kernel (conv_wgrad_halo.inc): off / images
- *                               whose sides are multiples of 8 / every such layer (default: the 8 x 8 patches overhang,
- *                               out-of-image pixels are fetched as zeros);  "wgrad_halo_stages" 2|3.
- *                               Its grid is one workgroup per 64 x 64 block of dw and slice: pass ~512 / blocks slices.
- *   "stem_pool_form" 0|1        passl_hip_bn_relu_maxpool_bwd_reduce: one 2048-item block per workgroup / workgroups that
- *                               walk over their share of the items with the next item's loads in flight (default; tensors
- *                               below 2^30 elements);  "stem_pool_wgs" n: workgroups of the latter (1024).  Both change
- *                               what passl_hip_bn_relu_maxpool_blocks returns: set them before sizing a slab.
- * Returns PASSL_EINVAL for an unknown name. */
+/* Tuning and diagnostic options: they choose kernels (defaults are tuned for MI355X; tests and A/B runs use them to
+ * force a path).  Each option takes its default, then, once, on the first access to any option, the value of the
+ * environment variable PASSL_<NAME in upper case> (igemm_ring: PASSL_IGEMM_RING) when that is set; a value that does not
+ * parse or is not accepted is reported on stderr and the default kept.  passl_hip_set_option then sets a value,
+ * passl_hip_get_option reads it back.  "any" = any int, a boolean is "!= 0".  The table: passl_amd/csrc/options.h.
+ *   name                   values        default
+ *   igemm_ring             any           1     the LDS-DMA ring conv kernel where it applies
+ *   igemm_ring_min_nk      any           8     ... only for reductions of at least n 64-element K-tiles
+ *   igemm_ring_min_tiles   any           1     ... and launches with at least n output tiles
+ *   igemm_ring_bm          128|256       128   its row tile: 128 (4 waves, 2 LDS stages, two workgroups per CU) or
+ *                                              256 (8 waves, 3 stages, one)
+ *   igemm_ring_bk          32|64         64    its K-tile
+ *   igemm_ring_stages32    3|4           4     ring depth of the BK = 32 form
+ *   igemm_8p               0..2          1     the 256 x 256-tile 8-phase kernel: never / when its cost model prefers it
+ *                                              to the ring kernel / whenever the launch is inside its envelope
+ *   igemm_8p_min_nk        >= 1          8     ... (mode 1) only for reductions of at least n 64-element K-tiles
+ *   igemm_8p_direct        any           1     ... its persistent form (stores from the accumulators)
+ *   igemm_8p_dense         0..2          1     ... its matrix-operand form: off / persistent form / also the staged form
+ *   igemm_8p_tk            >= 1          145   ... the cost model's constants (conv_igemm_8p.hip), in 0.01 us:
+ *   igemm_8p_te            >= 1          1000        per K-tile / per tile (prologue + epilogue) of the staged form,
+ *   igemm_8p_te_direct     >= 1          900         per tile of the persistent form,
+ *   igemm_8p_ring_tk       >= 1          112         per K-tile / per tile of the ring kernel;
+ *   igemm_8p_ring_te       >= 1          420
+ *   igemm_8p_margin        >= 1          100         margin in %
+ *   conv3x3_wave           any           1     the wave-per-patch kernel (conv3x3_wave.hip) for 3x3 / stride 1 / pad 1
+ *                                              launches with 64 input and 64 output channels whose image sides are
+ *                                              multiples of 8 (ResNet-50 stage 1, forward and data gradient)
+ *   conv3x3_wave_rows      4|8           4     ... 4 x 8 patches on eight waves / 8 x 8 patches on four
+ *   conv3x3_wave_modes     0..7          7     ... bit mask of the launches that take it: 1 plain / affine / ReLU,
+ *                                              2 fused statistics, 4 BatchNorm-backward sums
+ *   conv3x3_wave_dbg       any           0     ... ablation bits: 1 no statistics, 2 no epilogue, 4 no MFMA,
+ *                                              8 no halo loads
+ *   igemm_persist          any           0     persistent form of the register-staged kernel for dense 1x1 launches
+ *                                              (bit-identical, measured slower: profiles/r06_negative_results.txt)
+ *   igemm_persist_grid     >= 0          0     ... its grid, rounded down to a multiple of 8 (0: resident workgroups)
+ *   igemm_nk1              any           24    register-staged kernel: K-tiles up to which the single-stage form runs
+ *   igemm_lean             0|1           1     ... the 4-workgroup form of the single-K-tile dense launches
+ *   igemm_dbg              0..63         0     ... ablation bits: 1 no stores, 2 no epilogue, 4 no A loads, 8 no MFMA,
+ *                                              16 no statistics reduction, 32 no statistics arithmetic
+ *   stem_kernel            any           1     the dedicated kernel of the bf16 stem convolution (conv_stem.hip)
+ *   wgrad_dma              0|1           1     bf16 weight gradients through the LDS-DMA kernels
+ *   wgrad_tile             any           0     ... their tile: by shape / 1 64x64, 2 64x128, 3 128x64, 4 128x128
+ *   wgrad_pipe             any           2     ... the register double-buffered kernel: 0 off, 1 dense 128x128 shapes
+ *                                              with 4 x 32-row stages, 2 every shape with 2 x 64-row stages
+ *   wgrad_halo             0..2          2     spatially tiled 3x3 / stride 1 weight gradients (conv_wgrad_halo.inc):
+ *                                              off / images whose sides are multiples of 8 / every such layer (the
+ *                                              8 x 8 patches overhang, out-of-image pixels are fetched as zeros).  Its
+ *                                              grid is one workgroup per 64 x 64 block of dw and slice: pass ~512 /
+ *                                              blocks slices
+ *   wgrad_halo_stages      2|3           2     ... its LDS stages
+ *   wgrad_dbg              0|1           0     weight gradients: 1 skips the epilogue stores (ablation)
+ *   bn_stream_unroll       0|2|4|8       4     BatchNorm streaming kernels: grid-stride / tile form of U chunks per lane
+ *   stem_pool_form         0|1           1     passl_hip_bn_relu_maxpool_bwd_reduce: one 2048-item block per workgroup /
+ *                                              workgroups that walk over their share of the items with the next
+ *                                              item's loads in flight (tensors below 2^30 elements)
+ *   stem_pool_wgs          1..65536      1024  ... workgroups of the latter.  Both stem_pool options change what
+ *                                              passl_hip_bn_relu_maxpool_blocks returns: set them before sizing a slab
+ *   attn_f32mfma           0|1           0     bf16 attention through the exact-fp32-MFMA kernels
+ *   attn_waves             0|4|8         0     waves per workgroup of the bf16 attention kernels (0: by sequence length)
+ * passl_hip_set_option returns PASSL_EINVAL for an unknown name or a value outside the option's values. */
 int passl_hip_set_option(const char* name, int value);
+/* The current value of an option; PASSL_EINVAL for an unknown name or a NULL `value`. */
+int passl_hip_get_option(const char* name, int* value);
 /* Which kernel the most recent passl_hip_conv_igemm call of this process launched: 0 = igemm_kernel
  * (register-staged), 1 = igemm_ring_kernel, 2 = stem_kernel, 3 = igemm_8p_kernel, 4 = conv3x3_wave_kernel; -1
  * before the first call.

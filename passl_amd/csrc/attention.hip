@@ -18,8 +18,8 @@
 // KV-tiled (flash-style) variant.  The kernels in THIS file use exact-fp32 MFMA (bf16 inputs are
 // converted when staged): they serve fp32 activations (the parity dtype); bf16 activations take
 // the bf16-MFMA kernels of attention_bf16.hip.
-#include <stdlib.h>
 #include "common.h"
+#include "options.h"
 
 // attention_bf16.hip: bf16-MFMA kernels for bf16 activations
 int passl_attn_bf16_fwd(const void* qkv, void* out, float* lse, int B, int Tn, int H, int DH, float scale,
@@ -29,14 +29,8 @@ int passl_attn_bf16_bwd(const void* qkv, const void* out, const void* dout, cons
 
 namespace {
 
-// PASSL_ATTN_F32MFMA=1 routes bf16 activations through the exact-fp32-MFMA kernels (A/B runs)
-bool use_bf16_mfma() {
-  static const bool v = [] {
-    const char* e = getenv("PASSL_ATTN_F32MFMA");
-    return !(e && e[0] == '1');
-  }();
-  return v;
-}
+// option attn_f32mfma = 1 routes bf16 activations through the exact-fp32-MFMA kernels (A/B runs)
+bool use_bf16_mfma() { return !passl_opt(Opt::attn_f32mfma); }
 
 constexpr int kThreads = 256;
 constexpr int kMaxTiles = 13;

@@ -15,8 +15,8 @@
 //     receives channel i of the 4 rows) — no transposed copy of V / K / dO / Q is ever made.
 // Softmax statistics, exp, delta and all accumulators are fp32; P and dS are rounded to bf16 only
 // as MFMA operands.  8x fewer MFMA issue slots than the exact-fp32 kernels.
-#include <stdlib.h>
 #include "common.h"
+#include "options.h"
 
 namespace abf {
 
@@ -328,9 +328,9 @@ __global__ void __launch_bounds__(NW * 64) attn_bwd_kv_bf16_kernel(
 
 constexpr int max_lds(int DH) { return 2 * 224 * (DH + 8) * 2 + 2 * 224 * 4; }
 
-// PASSL_ATTN_WAVES=4 / 8 forces the workgroup size (A/B runs); default: 8 waves from 8 row tiles on
+// option attn_waves = 4 / 8 forces the workgroup size (A/B runs); default: 8 waves from 8 row tiles on
 inline bool eight_waves(int Tn, bool backward) {
-  static const int forced = [] { const char* e = getenv("PASSL_ATTN_WAVES"); return e ? atoi(e) : 0; }();
+  const int forced = passl_opt(Opt::attn_waves);
   if (forced == 4) return false;
   if (forced == 8) return true;
   // measured (scratch/bench_attn.py): the forward gains from 8 waves at every benchmark shape (faster staging even

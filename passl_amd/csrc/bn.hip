@@ -11,10 +11,9 @@
 //
 // Algorithmic bytes per activation (bf16): stats 2, apply 4 (+2 with residual),
 // bwd_reduce 6, bwd_apply 8 (+2 with residual).
-#include <stdlib.h>
-#include <string.h>
 #include <mutex>
 #include "common.h"
+#include "options.h"
 
 namespace {
 
@@ -522,8 +521,8 @@ __global__ void __launch_bounds__(kThreads) bn_bwd_apply_kernel(
 // to 2048).  One workgroup owns U * 256 CONSECUTIVE 16-byte chunks, a lane takes chunks
 // base + u * 256: every lane keeps ONE channel group (per-channel constants loaded once, ahead of the
 // data), the U data loads of a lane are issued back to back (U x 16 B in flight per lane instead of
-// one load per grid-stride iteration), and there is no loop.  g_stream_variant: 0 = the grid-stride
-// kernels above, U = 2 / 4 / 8 otherwise (passl_hip_set_option("bn_stream_unroll", U)).
+// one load per grid-stride iteration), and there is no loop.  Option bn_stream_unroll (options.h): 0 = the
+// grid-stride kernels above, U = 2 / 4 / 8 otherwise.
 template <typename T, int U>
 __global__ void __launch_bounds__(kThreads) bn_apply_tile_kernel(const T* __restrict__ x,
                                                                  const float* __restrict__ scale,
@@ -622,15 +621,6 @@ __global__ void __launch_bounds__(kThreads) bn_bwd_apply_tile_kernel(
   }
 }
 
-static int g_stream_unroll = -1;
-static inline int stream_unroll() {
-  if (g_stream_unroll < 0) {
-    const char* e = getenv("PASSL_BN_STREAM_UNROLL");
-    g_stream_unroll = e ? atoi(e) : 4;
-  }
-  return g_stream_unroll;
-}
-
 static inline int grid_for(int64_t n) {
   int64_t b = (n + kThreads - 1) / kThreads;
   if (b > 4096) b = 4096;
@@ -639,16 +629,6 @@ static inline int grid_for(int64_t n) {
 }
 
 }  // namespace
-
-// passl_hip_set_option("bn_stream_unroll", 0 | 2 | 4 | 8)   (runtime.hip dispatches)
-int passl_bn_option(const char* name, int value) {
-  if (!strcmp(name, "bn_stream_unroll")) {
-    if (value != 0 && value != 2 && value != 4 && value != 8) return PASSL_EINVAL;
-    g_stream_unroll = value;
-    return PASSL_OK;
-  }
-  return PASSL_EINVAL;
-}
 
 #define DISPATCH_DTYPE(dtype, ...)                          \
   if ((dtype) == PASSL_BF16) { using T = bf16_t; __VA_ARGS__ } \
@@ -744,7 +724,7 @@ extern "C" int passl_hip_bn_apply(const void* x, const float* scale, const float
     return PASSL_EINVAL;
   if (relu_mask && !relu) return PASSL_EINVAL;
   const int64_t nchunks = M * (C >> 3);
-  const int U = (kThreads % (C >> 3)) == 0 ? stream_unroll() : 0;
+  const int U = (kThreads % (C >> 3)) == 0 ? passl_opt(Opt::bn_stream_unroll) : 0;
 #define PASSL_BN_APPLY_TILE(UU)                                                                          \
   DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((bn_apply_tile_kernel<T, UU>),                               \
                                            dim3((unsigned)((nchunks + kThreads * UU - 1) / (kThreads * UU))), \
@@ -877,7 +857,7 @@ extern "C" int passl_hip_bn_bwd_apply(const void* dz, const void* z, const void*
       (C & 7) || !aligned16(dz) || !aligned16(x) || !aligned16(dx) || (dres && !aligned16(dres)))
     return PASSL_EINVAL;
   const int64_t nchunks = M * (C >> 3);
-  const int U = (kThreads % (C >> 3)) == 0 ? stream_unroll() : 0;
+  const int U = (kThreads % (C >> 3)) == 0 ? passl_opt(Opt::bn_stream_unroll) : 0;
 #define PASSL_BN_BWD_APPLY_TILE(UU)                                                                      \
   DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((bn_bwd_apply_tile_kernel<T, UU>),                           \
                                            dim3((unsigned)((nchunks + kThreads * UU - 1) / (kThreads * UU))), \

@@ -31,11 +31,10 @@
 // Envelope (passl_conv3x3_wave_try returns PASSL_EUNSUPPORTED outside it and the ring kernel takes the launch):
 // R = S = 3, stride 1, pad 1, C = NCOLS = 64, bf16 in / out, dense NHWC operands, IH and IW multiples of 8, no residual;
 // epilogues: affine (+ReLU), forward statistics, BatchNorm-backward statistics with the ReLU mask recomputed from y
-// (bnb_relu 0 or 2).  Option conv3x3_wave = 0 / 1 (passl_hip_set_option, PASSL_CONV3X3_WAVE).
-#include <stdlib.h>
-#include <string.h>
+// (bnb_relu 0 or 2).  Options (options.h): conv3x3_wave, conv3x3_wave_rows, conv3x3_wave_modes, conv3x3_wave_dbg.
 #include "igemm_dma.h"
 #include "igemm_epi.h"
+#include "options.h"
 
 namespace w3 {
 
@@ -471,28 +470,8 @@ static int dispatch(const passl_conv_desc* d, Params& p, hipStream_t st) {
 
 }  // namespace w3
 
-static int g_w3 = -1, g_w3_dbg = 0, g_w3_rows = 4, g_w3_modes = 7;
-int passl_conv3x3_wave_option(const char* name, int value) {
-  if (!strcmp(name, "conv3x3_wave_dbg")) { g_w3_dbg = value; return PASSL_OK; }
-  // which launches take the kernel (in-step experiments): bit 0 = plain / affine / ReLU epilogues (the key encoder's
-  // folded BatchNorm, evaluation), bit 1 = forward with fused statistics, bit 2 = data gradient with the BatchNorm-backward sums
-  if (!strcmp(name, "conv3x3_wave_modes")) { g_w3_modes = value & 7; return PASSL_OK; }
-  if (!strcmp(name, "conv3x3_wave_rows")) {          // 8: four waves x (8 x 8 patches); 4: eight waves x (4 x 8 patches)
-    if (value != 4 && value != 8) return PASSL_EINVAL;
-    g_w3_rows = value;
-    return PASSL_OK;
-  }
-  if (strcmp(name, "conv3x3_wave")) return PASSL_EINVAL;
-  g_w3 = value != 0;
-  return PASSL_OK;
-}
-
 int passl_conv3x3_wave_try(const passl_conv_desc* d, hipStream_t st) {
-  if (g_w3 < 0) {
-    const char* e = getenv("PASSL_CONV3X3_WAVE");
-    g_w3 = e ? (atoi(e) != 0) : 1;
-  }
-  if (!g_w3) return PASSL_EUNSUPPORTED;
+  if (!passl_opt(Opt::conv3x3_wave)) return PASSL_EUNSUPPORTED;
   if (d->dtype != PASSL_BF16 || d->out_f32 || d->residual) return PASSL_EUNSUPPORTED;
   if (d->R != 3 || d->S != 3 || d->sh != 1 || d->sw != 1 || d->ph != 1 || d->pw != 1) return PASSL_EUNSUPPORTED;
   if (d->C != w3::kC || d->NCOLS != w3::kC || d->IH != d->OP || d->IW != d->OQ) return PASSL_EUNSUPPORTED;
@@ -503,7 +482,9 @@ int passl_conv3x3_wave_try(const passl_conv_desc* d, hipStream_t st) {
   const int64_t a_bytes = (int64_t)d->N * d->IH * d->IW * d->C * 2;
   if (a_bytes >= 0x7ffffff0ll) return PASSL_EUNSUPPORTED;           // 32-bit buffer offsets, also for the output
   if (d->stats && d->bnb_partial) return PASSL_EUNSUPPORTED;
-  if (!((g_w3_modes >> (d->stats ? 1 : d->bnb_partial ? 2 : 0)) & 1)) return PASSL_EUNSUPPORTED;
+  // which launches take the kernel (in-step experiments): bit 0 = plain / affine / ReLU epilogues (the key encoder's
+  // folded BatchNorm, evaluation), bit 1 = forward with fused statistics, bit 2 = data gradient with the BatchNorm-backward sums
+  if (!((passl_opt(Opt::conv3x3_wave_modes) >> (d->stats ? 1 : d->bnb_partial ? 2 : 0)) & 1)) return PASSL_EUNSUPPORTED;
   if (d->bnb_partial && (d->relu || d->scale || d->shift || (d->bnb_relu != 0 && d->bnb_relu != 2) || d->bnb2_partial))
     return PASSL_EUNSUPPORTED;
   if (d->stats && (d->relu || d->scale || d->shift)) return PASSL_EUNSUPPORTED;
@@ -519,6 +500,7 @@ int passl_conv3x3_wave_try(const passl_conv_desc* d, hipStream_t st) {
   p.a_bytes = (uint32_t)a_bytes;
   p.N = d->N; p.IH = d->IH; p.IW = d->IW;
   p.relu = d->relu;
-  p.dbg = g_w3_dbg;
-  return g_w3_rows == 8 ? w3::dispatch<8>(d, p, st) : w3::dispatch<4>(d, p, st);
+  p.dbg = passl_opt(Opt::conv3x3_wave_dbg);
+  // rows 8: four waves x (8 x 8 patches); 4: eight waves x (4 x 8 patches)
+  return passl_opt(Opt::conv3x3_wave_rows) == 8 ? w3::dispatch<8>(d, p, st) : w3::dispatch<4>(d, p, st);
 }

@@ -35,9 +35,9 @@
 //   MEASURED (profiles/r06_kbench_persist.txt): exact, and 10-26 % SLOWER than one tile per workgroup — the staging registers
 //   that stay live across the epilogue cost the kernel half its workgroups per CU (229 VGPRs: 2 instead of 3-4), and the
 //   store phase is bound by how many waves issue stores, not by their acknowledgements.  OPT-IN (igemm_persist=1).
-#include <stdlib.h>
 #include "common.h"
 #include "igemm_epi.h"
+#include "options.h"
 #include "prof.h"
 
 namespace {
@@ -96,7 +96,7 @@ struct Params {
   int relu, out_f32;
   int tiles_n, ntiles;
   FastDiv d_opq, d_oq, d_tn;
-  int dbg;   // ablation switches for tuning runs (PASSL_IGEMM_DBG): 1 no stores, 2 no epilogue, 4 no A loads, 8 no MFMA
+  int dbg;   // ablation switches for tuning runs (option igemm_dbg): 1 no stores, 2 no epilogue, 4 no A loads, 8 no MFMA
 };
 
 __device__ __forceinline__ int swz(int row, int slot) { return slot ^ ((row >> 1) & 7); }
@@ -433,8 +433,6 @@ __global__ void __launch_bounds__(kThreads, PERSIST ? 2 : (LEAN ? 4 : ((STAGES =
   }
 }
 
-static int g_persist = -1, g_persist_grid = 0;
-
 template <typename T, int BM, int BN, bool GENERIC, int STAGES, bool EPI32, bool DENSE, bool LEAN = false, bool BNB2 = false,
           bool PERSIST = false>
 int launch(const Params& p, hipStream_t st) {
@@ -456,37 +454,18 @@ int launch(const Params& p, hipStream_t st) {
     }
     attr_set = true;
   }
-  const int slots = (PERSIST && g_persist_grid >= 8) ? g_persist_grid : wg_slots;
+  const int grid_opt = passl_opt(Opt::igemm_persist_grid) & ~7;      // 0: as many workgroups as the device holds
+  const int slots = (PERSIST && grid_opt >= 8) ? grid_opt : wg_slots;
   const int grid = (PERSIST && p.ntiles > slots) ? slots : p.ntiles;
   hipLaunchKernelGGL((igemm_kernel<T, BM, BN, GENERIC, STAGES, EPI32, DENSE, LEAN, BNB2, PERSIST>), dim3(grid),
                      dim3(kThreads), LDS, st, p);
   return hipGetLastError() == hipSuccess ? PASSL_OK : PASSL_ELAUNCH;
 }
 
-// igemm_persist: 0 = one tile per workgroup (rounds 1-5), 1 = the persistent form for dense bf16 launches whose tiles
-// outnumber the resident workgroups (passl_hip_set_option("igemm_persist", v) / PASSL_IGEMM_PERSIST)
-}  // namespace
-int passl_igemm_persist_option(int value) { g_persist = value != 0; return PASSL_OK; }
-// igemm_persist_grid: 0 = as many workgroups as the device holds (default); n = that many (tests: small launches walk several tiles)
-int passl_igemm_persist_grid_option(int value) { g_persist_grid = value < 0 ? 0 : (value & ~7); return PASSL_OK; }
-namespace {
-static bool persist_on() {
-  if (g_persist < 0) {
-    const char* e = getenv("PASSL_IGEMM_PERSIST");
-    g_persist = e ? (atoi(e) != 0) : 0;      // measured SLOWER (profiles/r06_negative_results.txt #1): opt-in
-  }
-  return g_persist != 0;
-}
-
-// K-tiles up to which the single-LDS-stage variant is used (tunable: PASSL_IGEMM_NK1)
-int nk1_threshold() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("PASSL_IGEMM_NK1");
-    v = e ? atoi(e) : 24;
-  }
-  return v;
-}
+// igemm_persist: 0 = one tile per workgroup (rounds 1-5; default: the persistent form measured SLOWER,
+// profiles/r06_negative_results.txt #1), 1 = the persistent form for dense bf16 launches whose tiles outnumber the
+// resident workgroups; igemm_persist_grid: its grid (tests: small launches walk several tiles)
+bool persist_on() { return passl_opt(Opt::igemm_persist) != 0; }
 
 template <typename T, int BN>
 int dispatch(const Params& p, bool generic, bool out_f32, bool dense, int nk, hipStream_t st) {
@@ -497,13 +476,12 @@ int dispatch(const Params& p, bool generic, bool out_f32, bool dense, int nk, hi
     if (out_f32)
       return generic ? PASSL_EUNSUPPORTED : launch<T, 128, BN, false, 2, true, false>(p, st);
     if (generic) return launch<T, 128, BN, true, 2, false, false>(p, st);
-    const bool one = nk <= nk1_threshold();
+    const bool one = nk <= passl_opt(Opt::igemm_nk1);     // K-tiles up to which the single-LDS-stage variant is used
     // LEAN: single-K-tile dense launches without residual / BatchNorm-backward work in the epilogue (the
     // K = 64 forward 1x1 layers of stage 1) fit 116 VGPRs -> 4 workgroups per CU instead of 3: these
     // launches are bound by how many operand waits / epilogues a CU has in flight;
-    // 64->256 @56: 117.6 -> 101.1 us, with statistics 152.9 -> 127.0 us.  PASSL_IGEMM_LEAN=0 disables.
-    static const bool lean_on = !(getenv("PASSL_IGEMM_LEAN") && atoi(getenv("PASSL_IGEMM_LEAN")) == 0);
-    if (dense && lean_on && nk == 1 && !p.res && !p.bnb_partial)
+    // 64->256 @56: 117.6 -> 101.1 us, with statistics 152.9 -> 127.0 us.  Option igemm_lean = 0 disables.
+    if (dense && passl_opt(Opt::igemm_lean) && nk == 1 && !p.res && !p.bnb_partial)
       return persist_on() ? launch<T, 128, BN, false, 1, false, true, true, false, true>(p, st)
                           : launch<T, 128, BN, false, 1, false, true, true>(p, st);
     if (dense && one && persist_on()) return launch<T, 128, BN, false, 1, false, true, false, false, true>(p, st);
@@ -573,13 +551,7 @@ extern "C" int passl_hip_conv_igemm(const passl_conv_desc* d, passl_stream_t str
   p.a_sn = d->a_sn; p.a_sh = d->a_sh; p.a_sw = d->a_sw;
   p.y_sn = d->y_sn; p.y_sh = d->y_sh; p.y_sw = d->y_sw;
   p.relu = d->relu; p.out_f32 = d->out_f32;
-  {
-    static int dbg = -1;
-    static int dyn = -1;
-    if (dyn < 0) dyn = getenv("PASSL_IGEMM_DBG_DYNAMIC") ? 1 : 0;
-    if (dbg < 0 || dyn) { const char* e = getenv("PASSL_IGEMM_DBG"); dbg = e ? atoi(e) : 0; }
-    p.dbg = dbg;
-  }
+  p.dbg = passl_opt(Opt::igemm_dbg);
   const bool generic = (d->C % bk) != 0;
   const bool narrow = d->NCOLS <= 64;
   const int bn = narrow ? 64 : 128;
@@ -621,7 +593,7 @@ extern "C" int passl_hip_conv_igemm(const passl_conv_desc* d, passl_stream_t str
       g_last_kernel = 1;
       return rc2;
     }
-    if (nk > nk1_threshold()) return PASSL_EUNSUPPORTED;
+    if (nk > passl_opt(Opt::igemm_nk1)) return PASSL_EUNSUPPORTED;
     passl_prof_begin(2, st);
     const int rc2 = persist_on() ? launch<bf16_t, 128, 128, false, 1, false, true, false, true, true>(p, st)
                                  : launch<bf16_t, 128, 128, false, 1, false, true, false, true>(p, st);

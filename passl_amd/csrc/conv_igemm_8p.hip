@@ -44,6 +44,7 @@
 // the 256 CUs well enough (passl_igemm_8p_try).
 #include "igemm_dma.h"
 #include "igemm_epi.h"
+#include "options.h"
 
 namespace g8 {
 
@@ -74,8 +75,7 @@ typedef std::integral_constant<int, 1> I1;
 // walk, the per-tap bounds checks and the image decomposition of a row drop out of the instruction stream and of the
 // scalar register file (the general form keeps ~20 more scalars live and spills 69 of them to lanes:
 // profiles/r03_kernel_resources.txt).  Same arithmetic, same order, same bits (profiles/r04_8p_dense_ab.txt).
-// passl_hip_set_option("igemm_8p_dense", v) / PASSL_IGEMM_8P_DENSE=v: 0 off, 1 the persistent form (default),
-// 2 also the staged (fused-statistics) form.
+// Option igemm_8p_dense (options.h): 0 off, 1 the persistent form (default), 2 also the staged (fused-statistics) form.
 template <bool DIRECT, bool DENSE = false>
 __global__ void __launch_bounds__(kThreads) igemm_8p_kernel(const Params p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -514,67 +514,40 @@ static int launch(const Params& p, hipStream_t st) {
 // with nk = 64-element K-tiles, tk / rtk the time of one K-tile and te / rte the exposed prologue + epilogue of
 // a tile (the staged 8-phase form's is larger: nothing else runs on the CU while a tile is stored; the persistent
 // form — igemm_8p_direct, default on — hides most of it: te_direct).
-static int g_8p_mode = -1, g_8p_min_nk = 8, g_8p_tk = 145, g_8p_te = 1000, g_8p_ted = 900, g_8p_rtk = 112,
-           g_8p_rte = 420, g_8p_margin = 100, g_8p_direct = 1, g_8p_dense = -1;
-
-int passl_igemm_8p_option(const char* name, int value) {
-  if (!strcmp(name, "igemm_8p")) {
-    if (value < 0 || value > 2) return PASSL_EINVAL;
-    g_8p_mode = value;
-    return PASSL_OK;
-  }
-  if (!strcmp(name, "igemm_8p_direct")) { g_8p_direct = value != 0; return PASSL_OK; }
-  if (!strcmp(name, "igemm_8p_dense")) {              // 0 off (default), 1 persistent form, 2 also the staged form
-    if (value < 0 || value > 2) return PASSL_EINVAL;
-    g_8p_dense = value;
-    return PASSL_OK;
-  }
-  int* slot = !strcmp(name, "igemm_8p_min_nk") ? &g_8p_min_nk : !strcmp(name, "igemm_8p_tk") ? &g_8p_tk :
-              !strcmp(name, "igemm_8p_te") ? &g_8p_te : !strcmp(name, "igemm_8p_te_direct") ? &g_8p_ted : !strcmp(name, "igemm_8p_ring_tk") ? &g_8p_rtk :
-              !strcmp(name, "igemm_8p_ring_te") ? &g_8p_rte : !strcmp(name, "igemm_8p_margin") ? &g_8p_margin : nullptr;
-  if (!slot) return PASSL_EINVAL;
-  if (value <= 0) return PASSL_EINVAL;
-  *slot = value;
-  return PASSL_OK;
-}
-
+// Options (options.h): igemm_8p (the mode), igemm_8p_min_nk, the cost model's constants igemm_8p_tk / _te / _te_direct /
+// _ring_tk / _ring_te / _margin, igemm_8p_direct, igemm_8p_dense.
 int passl_igemm_8p_try(const passl_conv_desc* d, hipStream_t st) {
-  if (g_8p_mode < 0) {
-    const char* e = getenv("PASSL_IGEMM_8P");
-    g_8p_mode = e ? atoi(e) : 1;
-    if (g_8p_mode < 0 || g_8p_mode > 2) g_8p_mode = 1;
-  }
-  if (g_8p_mode == 0) return PASSL_EUNSUPPORTED;
+  const int mode = passl_opt(Opt::igemm_8p);
+  if (mode == 0) return PASSL_EUNSUPPORTED;
   ring::Params p;
   if (!ring::fill_params(d, g8::BM, g8::BN, p)) return PASSL_EUNSUPPORTED;
   const int nk = p.KDIM / g8::BK;
   // the persistent form stores from the accumulators: launches with fused statistics keep the staged epilogue
-  const bool direct = g_8p_direct && nk >= 2 && !d->stats && !d->bnb_partial;
-  if (g_8p_mode == 1) {
+  const bool direct = passl_opt(Opt::igemm_8p_direct) && nk >= 2 && !d->stats && !d->bnb_partial;
+  if (mode == 1) {
     // short reductions: igemm_kernel's territory (also inside the step: taking the K = 256 launches of stages 3 / 4
     // here — 4 K-tiles, <= 800 tiles — measured 24.4 vs 24.1 ms per MoCo step, profiles/r05_negative_results.txt)
-    if (nk < g_8p_min_nk) return PASSL_EUNSUPPORTED;
+    if (nk < passl_opt(Opt::igemm_8p_min_nk)) return PASSL_EUNSUPPORTED;
     const int64_t t8 = p.ntiles;
     const int64_t tr = ((int64_t)(p.M + 127) / 128) * ((d->NCOLS + 127) / 128);
-    const double time8 = (double)((t8 + 255) / 256) * ((double)nk * g_8p_tk + (direct ? g_8p_ted : g_8p_te));
+    const double time8 = (double)((t8 + 255) / 256) *
+                         ((double)nk * passl_opt(Opt::igemm_8p_tk) +
+                          passl_opt(direct ? Opt::igemm_8p_te_direct : Opt::igemm_8p_te));
     // the ring kernel's workgroups drift apart, so large launches cost tiles / 512 "rounds"; a short launch
     // pays for its last, partly filled round (measured: 1.53 rounds cost 1.8, 3.06 cost 3.7)
     double rr = (double)tr / 512.0;
     if (rr < 4.0) rr = (double)((int64_t)(rr * 2.0 + 0.999)) * 0.5;
-    const double timer = (rr < 1.0 ? 1.0 : rr) * ((double)nk * g_8p_rtk + g_8p_rte);
-    if (time8 * g_8p_margin >= timer * 100.0) return PASSL_EUNSUPPORTED;
+    const double timer =
+        (rr < 1.0 ? 1.0 : rr) * ((double)nk * passl_opt(Opt::igemm_8p_ring_tk) + passl_opt(Opt::igemm_8p_ring_te));
+    if (time8 * passl_opt(Opt::igemm_8p_margin) >= timer * 100.0) return PASSL_EUNSUPPORTED;
   }
-  if (g_8p_dense < 0) {
-    const char* e = getenv("PASSL_IGEMM_8P_DENSE");
-    g_8p_dense = e ? atoi(e) : 1;
-    if (g_8p_dense < 0 || g_8p_dense > 2) g_8p_dense = 1;
-  }
+  const int dense = passl_opt(Opt::igemm_8p_dense);
   // the matrix-operand specialisation.  1 (default since round 4): every plain-matrix launch of the persistent form —
   // the ViT Linears and the 1x1 stride-1 convolutions without fused statistics; bit-identical to the general form on
   // every shape of scratch/ab_8p_dense.py incl. ragged tiles and 4-13 % faster on 8 of the 9 shapes this kernel takes
   // (the K = 512 -> 2048 Linear is 6 % slower; profiles/r04_8p_dense_ab.txt), GPU suite green with it.  2 (opt-in): also the launches with fused statistics
   // (staged form) — exact as well, but faster on only 2 of 4 R50 shapes (256->1024 @14 is 8 % slower).
-  if (g_8p_dense >= 1 && p.dense && direct) return g8::launch<true, true>(p, st);
-  if (g_8p_dense >= 2 && p.dense && !direct) return g8::launch<false, true>(p, st);
+  if (dense >= 1 && p.dense && direct) return g8::launch<true, true>(p, st);
+  if (dense >= 2 && p.dense && !direct) return g8::launch<false, true>(p, st);
   return direct ? g8::launch<true>(p, st) : g8::launch<false>(p, st);
 }

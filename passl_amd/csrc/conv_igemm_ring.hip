@@ -24,6 +24,7 @@
 // with 32-bit byte offsets; passl_hip_conv_igemm falls back to igemm_kernel otherwise.
 #include "igemm_dma.h"
 #include "igemm_epi.h"
+#include "options.h"
 
 namespace ring {
 
@@ -340,54 +341,24 @@ int launch(const Params& p, hipStream_t st) {
 
 // Returns PASSL_EUNSUPPORTED when the descriptor is outside this kernel's envelope (the caller
 // then uses igemm_kernel); the descriptor has already been validated by passl_hip_conv_igemm.
-static int g_ring_enabled = -1, g_ring_min_tiles = 1, g_ring_bm = 128, g_ring_min_nk = 8, g_ring_bk = 64,
-           g_ring_stages32 = 4;
-
-// passl_hip_set_option("igemm_ring", 0/1) / ("igemm_ring_min_tiles", n)   (runtime.hip dispatches)
-int passl_igemm_ring_option(const char* name, int value) {
-  if (!strcmp(name, "igemm_ring")) { g_ring_enabled = value != 0; return PASSL_OK; }
-  if (!strcmp(name, "igemm_ring_min_tiles")) { g_ring_min_tiles = value; return PASSL_OK; }
-  if (!strcmp(name, "igemm_ring_min_nk")) { g_ring_min_nk = value; return PASSL_OK; }
-  if (!strcmp(name, "igemm_ring_stages32")) {       // ring depth of the BK = 32 variant: 3 (3 WG/CU) or 4
-    if (value != 3 && value != 4) return PASSL_EINVAL;
-    g_ring_stages32 = value;
-    return PASSL_OK;
-  }
-  if (!strcmp(name, "igemm_ring_bk")) {
-    if (value != 64 && value != 32) return PASSL_EINVAL;
-    g_ring_bk = value;
-    return PASSL_OK;
-  }
-  if (!strcmp(name, "igemm_ring_bm")) {
-    if (value != 128 && value != 256) return PASSL_EINVAL;
-    g_ring_bm = value;
-    return PASSL_OK;
-  }
-  return PASSL_EINVAL;
-}
-
+// Options (options.h): igemm_ring, igemm_ring_min_nk, igemm_ring_min_tiles, igemm_ring_bm, igemm_ring_bk,
+// igemm_ring_stages32 (ring depth of the BK = 32 variant: 3 -> 3 workgroups per CU, or 4).
 int passl_igemm_ring_try(const passl_conv_desc* d, hipStream_t st) {
-  if (g_ring_enabled < 0) {
-    const char* e = getenv("PASSL_IGEMM_RING");
-    g_ring_enabled = e ? atoi(e) : 1;
-    const char* t = getenv("PASSL_IGEMM_RING_MIN_TILES");
-    if (t) g_ring_min_tiles = atoi(t);
-  }
-  const int enabled = g_ring_enabled, min_tiles = g_ring_min_tiles;
-  if (!enabled) return PASSL_EUNSUPPORTED;
+  if (!passl_opt(Opt::igemm_ring)) return PASSL_EUNSUPPORTED;
   // short reductions are dominated by the prologue/epilogue: igemm_kernel's single-stage variant
   // (3 workgroups per CU) wins there (measured per layer: profiles/r01_ring_vs_igemm_bs256.txt)
-  if ((int64_t)d->R * d->S * d->C < 64ll * g_ring_min_nk) return PASSL_EUNSUPPORTED;
+  if ((int64_t)d->R * d->S * d->C < 64ll * passl_opt(Opt::igemm_ring_min_nk)) return PASSL_EUNSUPPORTED;
   const int bn = d->NCOLS <= 64 ? 64 : 128;
-  const int bm = g_ring_bm;
+  const int bm = passl_opt(Opt::igemm_ring_bm);
   if (bm != 128 && (d->stats || d->bnb_partial)) return PASSL_EUNSUPPORTED;   // slabs are per 128-row tile
   ring::Params p;
   if (!ring::fill_params(d, bm, bn, p)) return PASSL_EUNSUPPORTED;
-  if (p.ntiles < min_tiles) return PASSL_EUNSUPPORTED;
+  if (p.ntiles < passl_opt(Opt::igemm_ring_min_tiles)) return PASSL_EUNSUPPORTED;
   if (bm == 256) return bn == 64 ? ring::launch<256, 64, 3>(p, st) : ring::launch<256, 128, 3>(p, st);
-  if (g_ring_bk == 32 && g_ring_stages32 == 3)
+  const int bk = passl_opt(Opt::igemm_ring_bk);
+  if (bk == 32 && passl_opt(Opt::igemm_ring_stages32) == 3)
     return bn == 64 ? ring::launch<128, 64, 3, 32>(p, st) : ring::launch<128, 128, 3, 32>(p, st);
-  if (g_ring_bk == 32) return bn == 64 ? ring::launch<128, 64, 4, 32>(p, st) : ring::launch<128, 128, 4, 32>(p, st);
+  if (bk == 32) return bn == 64 ? ring::launch<128, 64, 4, 32>(p, st) : ring::launch<128, 128, 4, 32>(p, st);
   return bn == 64 ? ring::launch<128, 64, 2>(p, st) : ring::launch<128, 128, 2>(p, st);
 }
 

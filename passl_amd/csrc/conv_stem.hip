@@ -26,10 +26,9 @@
 //    one 8 x 16 tile here (any partition into 128-element groups serves bn_finalize).
 //
 // Used for OP % 8 == 0, OQ % 16 == 0 (224^2 inputs: 112 x 112); everything else stays on igemm_kernel.
-#include <stdlib.h>
-#include <string.h>
 #include "common.h"
 #include "igemm_epi.h"
+#include "options.h"
 
 namespace stem {
 
@@ -178,23 +177,10 @@ __global__ void __launch_bounds__(kThreads, 3) stem_kernel(const Params p) {
 }  // namespace stem
 
 // PASSL_EUNSUPPORTED when the descriptor is not the bf16 stem launch this kernel covers (the caller
-// then uses igemm_kernel); the descriptor has already been validated by passl_hip_conv_igemm.
-static int g_stem_enabled = -1;
-
-// passl_hip_set_option("stem_kernel", 0/1)   (runtime.hip dispatches)
-int passl_stem_option(const char* name, int value) {
-  if (strcmp(name, "stem_kernel")) return PASSL_EINVAL;
-  g_stem_enabled = value != 0;
-  return PASSL_OK;
-}
-
+// then uses igemm_kernel); the descriptor has already been validated by passl_hip_conv_igemm.  Option stem_kernel.
 int passl_stem_try(const passl_conv_desc* d, hipStream_t st) {
-  if (g_stem_enabled < 0) {
-    const char* e = getenv("PASSL_STEM_KERNEL");
-    g_stem_enabled = e ? atoi(e) : 1;
-  }
-  const int enabled = g_stem_enabled;
-  if (!enabled || d->dtype != PASSL_BF16 || d->out_f32 || d->bnb_partial || d->residual) return PASSL_EUNSUPPORTED;
+  if (!passl_opt(Opt::stem_kernel) || d->dtype != PASSL_BF16 || d->out_f32 || d->bnb_partial || d->residual)
+    return PASSL_EUNSUPPORTED;
   if (d->R != 7 || d->S != 1 || d->C != 32 || d->sh != 2 || d->sw != 1 || d->ph != 0 || d->pw != 0 ||
       d->NCOLS != 64 || d->a_sw != 8)
     return PASSL_EUNSUPPORTED;

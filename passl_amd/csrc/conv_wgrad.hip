@@ -13,10 +13,9 @@
 // The reduction over M is split over blockIdx.z; partial tiles are accumulated with fp32
 // global atomics (dW is zeroed by the caller).  Per-row gather info (image base, ih0, iw0) for
 // the next reduction tile is computed by 64 threads into a double-buffered LDS table.
-#include <stdlib.h>
-#include <string.h>
 #include <type_traits>
 #include "common.h"
+#include "options.h"
 #include "prof.h"
 #include "wgrad_halo_geom.h"
 
@@ -35,7 +34,7 @@ struct WParams {
   int tiles_per_split, nk_total;
   float* ws;        // split-M partial tiles [splits][NCOLS][KDIM] (fixed-order reduction afterwards) or null
   int nsplits;      // number of M-slices of this launch
-  int dbg;   // tuning switches (PASSL_WGRAD_DBG): 1 = skip the epilogue stores
+  int dbg;   // tuning switches (option wgrad_dbg): 1 = skip the epilogue stores
   int grid_j, grid_oc;   // tile counts of the 1-D launch of wgrad_dma_kernel
 };
 
@@ -843,12 +842,6 @@ int launch_dma(const WParams& p, int splits, uint32_t a_bytes, uint32_t dy_bytes
 
 #include "conv_wgrad_halo.inc"
 
-int g_wgrad_tile = 0;     // 0 = by shape; 1 = 64x64, 2 = 64x128, 3 = 128x64, 4 = 128x128 (experiments)
-
-// wgrad_pipe_kernel (register double-buffered fragments): 2 = 2 x 64-row stages for every shape (default),
-// 3 = same, 1 = 4 x 32-row stages for dense 128x128 shapes only, 0 = wgrad_dma_kernel everywhere
-int g_wgrad_pipe = 2;
-
 // x is a contiguous [M][C] matrix: 1x1, stride 1, no padding over a dense NHWC tensor (or a Linear)
 bool dense_rows(const WParams& p) {
   return p.R == 1 && p.S == 1 && p.sh == 1 && p.sw == 1 && p.ph == 0 && p.pw == 0 && p.OP == p.IH &&
@@ -856,12 +849,16 @@ bool dense_rows(const WParams& p) {
          p.a_sn == (int64_t)p.IH * p.IW * p.C;
 }
 
+// Options (options.h): wgrad_tile: 0 = by shape; 1 = 64x64, 2 = 64x128, 3 = 128x64, 4 = 128x128 (experiments);
+// wgrad_pipe: wgrad_pipe_kernel (register double-buffered fragments): 2 = 2 x 64-row stages for every shape (default),
+// 3 = same, 1 = 4 x 32-row stages for dense 128x128 shapes only, 0 = wgrad_dma_kernel everywhere
 int dispatch_dma(const WParams& p, int splits, int64_t a_bytes, int64_t dy_bytes, hipStream_t st) {
   const int64_t lim32 = 0x7ffffff0ll;
   const bool small = a_bytes < lim32 && dy_bytes < lim32;     // the first-generation kernel addresses globally
-  if (g_wgrad_pipe && g_wgrad_tile == 0) {
+  const int tile = passl_opt(Opt::wgrad_tile), pipe = passl_opt(Opt::wgrad_pipe);
+  if (pipe && tile == 0) {
     const bool m64 = p.NCOLS <= 64, n64 = p.KDIM <= 64;
-    if (g_wgrad_pipe == 1 && dense_rows(p) && !m64 && !n64)
+    if (pipe == 1 && dense_rows(p) && !m64 && !n64)
       return launch_pipe<128, 128, 32, 4, true>(p, splits, a_bytes, dy_bytes, st);
     if (dense_rows(p)) {
       if (m64 && n64) return launch_pipe<64, 64, 64, 2, true>(p, splits, a_bytes, dy_bytes, st);
@@ -869,7 +866,7 @@ int dispatch_dma(const WParams& p, int splits, int64_t a_bytes, int64_t dy_bytes
       if (n64) return launch_pipe<128, 64, 64, 2, true>(p, splits, a_bytes, dy_bytes, st);
       return launch_pipe<128, 128, 64, 2, true>(p, splits, a_bytes, dy_bytes, st);
     }
-    if (g_wgrad_pipe >= 2) {
+    if (pipe >= 2) {
       if (m64 && n64) return launch_pipe<64, 64, 64, 2, false>(p, splits, a_bytes, dy_bytes, st);
       if (m64) return launch_pipe<64, 128, 64, 2, false>(p, splits, a_bytes, dy_bytes, st);
       if (n64) return launch_pipe<128, 64, 64, 2, false>(p, splits, a_bytes, dy_bytes, st);
@@ -878,10 +875,10 @@ int dispatch_dma(const WParams& p, int splits, int64_t a_bytes, int64_t dy_bytes
   }
   if (!small) return PASSL_EUNSUPPORTED;
   const uint32_t a32 = (uint32_t)a_bytes, dy32 = (uint32_t)dy_bytes;
-  if (g_wgrad_tile == 1) return launch_dma<64, 64>(p, splits, a32, dy32, st);
-  if (g_wgrad_tile == 2) return launch_dma<64, 128>(p, splits, a32, dy32, st);
-  if (g_wgrad_tile == 3) return launch_dma<128, 64>(p, splits, a32, dy32, st);
-  if (g_wgrad_tile == 4) return launch_dma<128, 128>(p, splits, a32, dy32, st);
+  if (tile == 1) return launch_dma<64, 64>(p, splits, a32, dy32, st);
+  if (tile == 2) return launch_dma<64, 128>(p, splits, a32, dy32, st);
+  if (tile == 3) return launch_dma<128, 64>(p, splits, a32, dy32, st);
+  if (tile == 4) return launch_dma<128, 128>(p, splits, a32, dy32, st);
   const bool m64 = p.NCOLS <= 64, n64 = p.KDIM <= 64;
   if (m64 && n64) return launch_dma<64, 64>(p, splits, a32, dy32, st);
   if (m64) return launch_dma<64, 128>(p, splits, a32, dy32, st);
@@ -893,19 +890,6 @@ int dispatch_dma(const WParams& p, int splits, int64_t a_bytes, int64_t dy_bytes
 
 int passl_slab_reduce_launch(const float* ws, float* out, int64_t n, int slabs, int accumulate,
                              hipStream_t st);   // flat.hip
-
-int passl_wgrad_option(const char* name, int value) {
-  if (strcmp(name, "wgrad_tile") == 0) { g_wgrad_tile = value; return PASSL_OK; }
-  if (strcmp(name, "wgrad_pipe") == 0) { g_wgrad_pipe = value; return PASSL_OK; }
-  // spatially tiled 3x3 kernel (opt-in): 1 = images whose sides are multiples of 8, 2 = every 3x3 / stride-1 layer
-  if (strcmp(name, "wgrad_halo") == 0) { g_wgrad_halo = value < 0 ? 0 : (value > 2 ? 2 : value); return PASSL_OK; }
-  if (strcmp(name, "wgrad_halo_stages") == 0) {
-    if (value != 2 && value != 3) return PASSL_EINVAL;
-    g_wgrad_halo_nst = value;
-    return PASSL_OK;
-  }
-  return PASSL_EINVAL;
-}
 
 extern "C" int passl_hip_conv_wgrad(const passl_wgrad_desc* d, passl_stream_t stream) {
   if (!d || !d->a || !d->dy || !d->dw) return PASSL_EINVAL;
@@ -937,13 +921,7 @@ extern "C" int passl_hip_conv_wgrad(const passl_wgrad_desc* d, passl_stream_t st
   if (splits > p.nk_total) splits = p.nk_total;
   p.tiles_per_split = (p.nk_total + splits - 1) / splits;
   splits = (p.nk_total + p.tiles_per_split - 1) / p.tiles_per_split;
-  {
-    static int dyn = -1;
-    static int dbg = 0;
-    if (dyn < 0) dyn = getenv("PASSL_WGRAD_DBG_DYNAMIC") ? 1 : 0;
-    if (dyn || dbg == 0) { const char* e = getenv("PASSL_WGRAD_DBG"); dbg = e ? atoi(e) : 0; }
-    p.dbg = dbg;
-  }
+  p.dbg = passl_opt(Opt::wgrad_dbg);
   const int64_t n_out = (int64_t)d->NCOLS * K64;
   if (splits > 1 && !d->ws) return PASSL_EINVAL;      // partial tiles need their slabs (no fp32 atomics)
   if (splits > 1 && d->ws) {
@@ -955,8 +933,7 @@ extern "C" int passl_hip_conv_wgrad(const passl_wgrad_desc* d, passl_stream_t st
   int rc;
   // bf16: LDS-DMA + transpose-read kernel when both operands are addressable with 32-bit byte
   // offsets (buffer addressing); the register-staged kernel otherwise and for fp32
-  static int use_dma = -1;
-  if (use_dma < 0) { const char* e = getenv("PASSL_WGRAD_DMA"); use_dma = e ? atoi(e) : 1; }
+  const bool use_dma = passl_opt(Opt::wgrad_dma) != 0;
   const int64_t a_bytes = ((int64_t)d->N * d->a_sn) * 2;
   const int64_t dy_bytes = (M64 * d->dy_ld) * 2;
   const int64_t lim = 0x7ffffff0ll;

@@ -1,4 +1,4 @@
-// Spatially tiled 3x3 / stride-1 weight gradient (default since round 5; passl_hip_set_option("wgrad_halo", 0) / PASSL_WGRAD_HALO=0 turns it off); included by conv_wgrad.hip
+// Spatially tiled 3x3 / stride-1 weight gradient (default since round 5; option wgrad_halo = 0 turns it off); included by conv_wgrad.hip
 // inside its anonymous namespace (WParams, wg_store, lds_read_tr64).  Design and layout: wgrad_halo_geom.h.
 //
 // Workgroup = 4 waves (2 x 2), a 64 (oc) x 64 (c) block of dW for all nine taps: 36 accumulator fragments per wave.
@@ -188,8 +188,6 @@ __global__ void __launch_bounds__(kThreads, NST == 2 ? 2 : 1) wgrad_halo_kernel(
         }
 }
 
-int g_wgrad_halo = -1, g_wgrad_halo_nst = 2;
-
 // EUNSUPPORTED: switched off (the default) or outside the envelope
 template <int NST, bool OVERHANG>
 int launch_halo(const WParams& p, const wgh::Geom& g, int splits, hipStream_t st) {
@@ -206,11 +204,11 @@ int launch_halo(const WParams& p, const wgh::Geom& g, int splits, hipStream_t st
 }
 
 int wgrad_halo_try(const WParams& p0, int splits, int64_t a_bytes, int64_t dy_bytes, hipStream_t st) {
-  if (g_wgrad_halo < 0) { const char* e = getenv("PASSL_WGRAD_HALO"); g_wgrad_halo = e ? atoi(e) : 2; }
-  if (!g_wgrad_halo) return PASSL_EUNSUPPORTED;
+  const int halo = passl_opt(Opt::wgrad_halo);    // 1: images whose sides are multiples of 8, 2: every such layer
+  if (!halo) return PASSL_EUNSUPPORTED;
   if (p0.R != 3 || p0.S != 3 || p0.sh != 1 || p0.sw != 1 || p0.ph != 1 || p0.pw != 1) return PASSL_EUNSUPPORTED;
   if (p0.IH != p0.OP || p0.IW != p0.OQ) return PASSL_EUNSUPPORTED;
-  if (g_wgrad_halo == 1 && ((p0.IH & 7) || (p0.IW & 7))) return PASSL_EUNSUPPORTED;      // 2: also images that the patches overhang
+  if (halo == 1 && ((p0.IH & 7) || (p0.IW & 7))) return PASSL_EUNSUPPORTED;      // 2: also images that the patches overhang
   const int64_t lim = 0x7ffffff0ll;
   if (a_bytes >= lim || dy_bytes >= lim) return PASSL_EUNSUPPORTED;
   if ((int64_t)(p0.IH - 1) * p0.a_sh + (int64_t)(p0.IW - 1) * p0.a_sw + p0.C > p0.a_sn) return PASSL_EUNSUPPORTED;
@@ -231,7 +229,8 @@ int wgrad_halo_try(const WParams& p0, int splits, int64_t a_bytes, int64_t dy_by
   p.grid_j = (p.C + 63) / 64;
   p.grid_oc = (p.NCOLS + 63) / 64;
   p.nsplits = splits;
+  const int nst = passl_opt(Opt::wgrad_halo_stages);
   if ((p.IH & 7) || (p.IW & 7))
-    return g_wgrad_halo_nst == 3 ? launch_halo<3, true>(p, g, splits, st) : launch_halo<2, true>(p, g, splits, st);
-  return g_wgrad_halo_nst == 3 ? launch_halo<3, false>(p, g, splits, st) : launch_halo<2, false>(p, g, splits, st);
+    return nst == 3 ? launch_halo<3, true>(p, g, splits, st) : launch_halo<2, true>(p, g, splits, st);
+  return nst == 3 ? launch_halo<3, false>(p, g, splits, st) : launch_halo<2, false>(p, g, splits, st);
 }

@@ -18,7 +18,7 @@
 
 namespace epi {
 
-// tuning switches of the register-staged kernel (PASSL_IGEMM_DBG, conv_igemm.hip: Params::dbg); 0 for the other kernels
+// tuning switches of the register-staged kernel (option igemm_dbg, conv_igemm.hip: Params::dbg); 0 for the other kernels
 template <typename P> __device__ __forceinline__ auto dbg_of(const P& p, int) -> decltype(p.dbg) { return p.dbg; }
 template <typename P> __device__ __forceinline__ int dbg_of(const P&, long) { return 0; }
 

@@ -1,8 +1,15 @@
-// ABI version, error strings and the event-based kernel timing hooks.
+// ABI version, error strings, the tuning options and the event-based kernel timing hooks.
+#include <ctype.h>
+#include <errno.h>
+#include <limits.h>
+#include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
+#include <initializer_list>
 #include <mutex>
 #include <vector>
 #include "common.h"
+#include "options.h"
 #include "prof.h"
 
 namespace {
@@ -116,27 +123,89 @@ extern "C" int passl_hip_prof_event_overhead(int n, passl_stream_t stream, doubl
   return PASSL_OK;
 }
 
-int passl_igemm_ring_option(const char* name, int value);    // conv_igemm_ring.hip
-int passl_igemm_8p_option(const char* name, int value);      // conv_igemm_8p.hip
-int passl_wgrad_option(const char* name, int value);         // conv_wgrad.hip
-int passl_bn_option(const char* name, int value);            // bn.hip
-int passl_stem_option(const char* name, int value);          // conv_stem.hip
-int passl_pool_option(const char* name, int value);          // stem_pool.hip
-int passl_igemm_persist_option(int value);                   // conv_igemm.hip
-int passl_conv3x3_wave_option(const char* name, int value);  // conv3x3_wave.hip
-int passl_igemm_persist_grid_option(int value);
+// ---- tuning options: the table of options.h, defaults overridden by PASSL_<NAME> on the first access
+namespace {
+struct OptRow {
+  const char* name;
+  int def, lo, hi;
+  int n;          // > 0: the value must also be one of vals[0, n)
+  int vals[4];
+};
+constexpr int count(std::initializer_list<int> v) { return (int)v.size(); }
+#define ANY RANGE(INT_MIN, INT_MAX)
+#define RANGE(lo, hi) lo, hi, 0, {}
+#define ONE_OF(...) INT_MIN, INT_MAX, count({__VA_ARGS__}), {__VA_ARGS__}
+#define PASSL_OPT_ROW(name, def, values) {#name, def, values},
+constexpr OptRow kOpts[] = {PASSL_OPTION_LIST(PASSL_OPT_ROW)};
+#undef PASSL_OPT_ROW
+#undef ONE_OF
+#undef RANGE
+#undef ANY
+constexpr int kNumOpts = (int)Opt::kCount;
+static_assert(sizeof(kOpts) / sizeof(kOpts[0]) == kNumOpts, "options.h: one row per option");
+
+constexpr bool accepts(const OptRow& r, int v) {
+  if (v < r.lo || v > r.hi) return false;
+  for (int i = 0; i < r.n; ++i)
+    if (r.vals[i] == v) return true;
+  return r.n == 0;
+}
+constexpr bool defaults_accepted() {
+  for (const OptRow& r : kOpts)
+    if (!accepts(r, r.def)) return false;
+  return true;
+}
+static_assert(defaults_accepted(), "options.h: a default outside its option's accepted values");
+
+int g_opt[kNumOpts];
+
+bool init_options() {
+  for (int i = 0; i < kNumOpts; ++i) {
+    const OptRow& r = kOpts[i];
+    g_opt[i] = r.def;
+    char var[64] = "PASSL_";
+    for (int k = 0; r.name[k]; ++k) var[6 + k] = (char)toupper((unsigned char)r.name[k]);
+    const char* e = getenv(var);
+    if (!e) continue;
+    char* end = nullptr;
+    errno = 0;
+    const long v = strtol(e, &end, 10);
+    if (!*e || *end || errno || v < INT_MIN || v > INT_MAX || !accepts(r, (int)v))
+      fprintf(stderr, "libpassl_hip: %s=%s is not a value of option %s: it keeps its default %d\n", var, e, r.name,
+              r.def);
+    else
+      g_opt[i] = (int)v;
+  }
+  return true;
+}
+
+int* opt_values() {
+  static const bool ready = init_options();
+  (void)ready;
+  return g_opt;
+}
+
+int opt_index(const char* name) {
+  for (int i = 0; name && i < kNumOpts; ++i)
+    if (!strcmp(name, kOpts[i].name)) return i;
+  return -1;
+}
+}  // namespace
+
+int passl_opt(Opt o) { return opt_values()[(int)o]; }
 
 extern "C" int passl_hip_set_option(const char* name, int value) {
-  if (!name) return PASSL_EINVAL;
-  if (!strcmp(name, "igemm_persist")) return passl_igemm_persist_option(value);
-  if (!strcmp(name, "igemm_persist_grid")) return passl_igemm_persist_grid_option(value);
-  if (passl_conv3x3_wave_option(name, value) == PASSL_OK) return PASSL_OK;
-  if (passl_wgrad_option(name, value) == PASSL_OK) return PASSL_OK;
-  if (passl_bn_option(name, value) == PASSL_OK) return PASSL_OK;
-  if (passl_stem_option(name, value) == PASSL_OK) return PASSL_OK;
-  if (passl_pool_option(name, value) == PASSL_OK) return PASSL_OK;
-  if (passl_igemm_8p_option(name, value) == PASSL_OK) return PASSL_OK;
-  return passl_igemm_ring_option(name, value);
+  const int i = opt_index(name);
+  if (i < 0 || !accepts(kOpts[i], value)) return PASSL_EINVAL;
+  opt_values()[i] = value;
+  return PASSL_OK;
+}
+
+extern "C" int passl_hip_get_option(const char* name, int* value) {
+  const int i = opt_index(name);
+  if (i < 0 || !value) return PASSL_EINVAL;
+  *value = opt_values()[i];
+  return PASSL_OK;
 }
 
 extern "C" int passl_hip_abi_version(void) { return PASSL_HIP_ABI_VERSION; }

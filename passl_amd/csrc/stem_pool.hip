@@ -19,8 +19,8 @@
 // per-channel sums are added in a different (fixed) order, i.e. agree to fp32 rounding.
 //
 // Replaces paddle.nn.BatchNorm2D + ReLU + MaxPool2D(3, 2, 1) of the stem (resnetimagenet.py:196-198) in training mode.
-#include <string.h>
 #include "common.h"
+#include "options.h"
 
 namespace {
 
@@ -498,12 +498,6 @@ __global__ void __launch_bounds__(kThreads, 2) bwd_reduce_kernel(const T* __rest
 
 }  // namespace v2
 
-// 1 (default): the second form of the reduce pass, 0: the first (the reference `kbench poolcheck` compares against,
-// and the form of tensors of 2^30 elements and more).  g_pool_wgs: workgroups of a second-form launch (2 per CU are
-// resident; 1024 = two rounds measured best).
-int g_pool_form = 1;
-int g_pool_wgs = 1024;
-
 bool shape_ok(int N, int H, int W, int C, int64_t* out_items, int64_t* in_items) {
   if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 7) || (kThreads % (C >> 3)) != 0) return false;
   const int P = (H + 2 - 3) / 2 + 1, Q = (W + 2 - 3) / 2 + 1;
@@ -521,31 +515,21 @@ v2::Geo make_geo(int N, int H, int W, int C, int64_t in_items) {
   while ((8u << g.cshift) < (uint32_t)C) ++g.cshift;
   g.total = (uint32_t)in_items;
   g.chunks = (uint32_t)((in_items + kThreads - 1) / kThreads);
-  const uint32_t wgs = (uint32_t)(g_pool_wgs > 0 ? g_pool_wgs : 1);
+  // option stem_pool_wgs: workgroups of a second-form launch (2 per CU are resident; 1024 = two rounds measured best)
+  const uint32_t wgs = (uint32_t)passl_opt(Opt::stem_pool_wgs);
   g.per_wg = (g.chunks + wgs - 1) / wgs;
   g.dW2 = v2::make_fdiv(g.W2); g.dH2 = v2::make_fdiv(g.H2);
   (void)N;
   return g;
 }
 inline int geo_blocks(const v2::Geo& g) { return (int)((g.chunks + g.per_wg - 1) / g.per_wg); }
-// the second form addresses with 32-bit element offsets
-inline bool second_form(int N, int H, int W, int C) { return g_pool_form == 1 && (int64_t)N * H * W * C < (1ll << 30); }
+// option stem_pool_form: 1 (default) the second form of the reduce pass, 0 the first (the reference `kbench poolcheck`
+// compares against).  The second form addresses with 32-bit element offsets: larger tensors take the first.
+inline bool second_form(int N, int H, int W, int C) {
+  return passl_opt(Opt::stem_pool_form) == 1 && (int64_t)N * H * W * C < (1ll << 30);
+}
 
 }  // namespace
-
-int passl_pool_option(const char* name, int value) {
-  if (strcmp(name, "stem_pool_form") == 0) {
-    if (value != 0 && value != 1) return PASSL_EINVAL;
-    g_pool_form = value;
-    return PASSL_OK;
-  }
-  if (strcmp(name, "stem_pool_wgs") == 0) {
-    if (value < 1 || value > 65536) return PASSL_EINVAL;
-    g_pool_wgs = value;
-    return PASSL_OK;
-  }
-  return PASSL_EINVAL;
-}
 
 #define DISPATCH_DTYPE(dtype, ...)                          \
   if ((dtype) == PASSL_BF16) { using T = bf16_t; __VA_ARGS__ } \

@@ -25,7 +25,8 @@ _state = {'device': None, 'dtype': torch.bfloat16,
           'stem_wgrad_main_last': os.environ.get('PASSL_STEM_WGRAD_MAIN_LAST', '1') != '0',
           # a weight gradient over at least this many rows is handed to the side stream at once (0: always batched)
           'side_urgent_rows': int(os.environ.get('PASSL_SIDE_URGENT_ROWS', '500000') or 0),
-          # the library reads the same variable (conv_wgrad_halo.inc): 0 off, 1 images with sides % 8 == 0, 2 all (default)
+          # the library's option wgrad_halo reads the same variable (csrc/options.h): 0 off, 1 images with sides % 8 == 0,
+          # 2 all (default); hip/lib.py pushes this value into the library when it loads it
           'wgrad_halo': int(os.environ.get('PASSL_WGRAD_HALO', '2') or 0)}
 
 

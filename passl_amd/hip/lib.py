@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), 'lib', 'libpassl_hip.so')
 
 F32, BF16 = 0, 1
-ABI_VERSION = 15          # include/passl_hip.h: PASSL_HIP_ABI_VERSION (the ctypes structs below mirror THAT layout)
+ABI_VERSION = 16          # include/passl_hip.h: PASSL_HIP_ABI_VERSION (the ctypes structs below mirror THAT layout)
 _DT = {torch.float32: F32, torch.bfloat16: BF16}
 
 c_p = C.c_void_p
@@ -62,6 +62,7 @@ SIGNATURES = {
     'passl_hip_abi_version': (c_i, []),
     'passl_hip_strerror': (C.c_char_p, [c_i]),
     'passl_hip_set_option': (c_i, [C.c_char_p, c_i]),
+    'passl_hip_get_option': (c_i, [C.c_char_p, C.POINTER(c_i)]),
     'passl_hip_last_igemm_kernel': (c_i, []),
     'passl_hip_ema_update': (c_i, [c_p, c_p, c_p, c_l, c_f, c_p]),
     'passl_hip_bn_fold': (c_i, [c_p, c_p, c_p, c_p, c_p, c_l, c_f, c_p, c_p, c_p]),
@@ -207,17 +208,14 @@ def load(path=None):
         fn.argtypes = args
     if path is None:
         _lib = lib
-        # PASSL_OPTIONS="name=value,name=value": passl_hip_set_option calls made once at load (kernel-selection A/Bs
-        # without touching code; an unknown name is an error, not a silent no-op)
+        # wgrad_halo is ONE switch with two readers (the library's kernel choice, config's slice count): Python's value
+        # goes first; PASSL_OPTIONS="name=value,name=value" then sets options through set_option, which keeps both
+        # readers in step (kernel-selection A/Bs without touching code; an unknown name is an error, not a no-op)
+        from . import config
+        set_option('wgrad_halo', config.wgrad_halo())
         for kv in filter(None, os.environ.get('PASSL_OPTIONS', '').split(',')):
             name, _, value = kv.partition('=')
-            check(lib.passl_hip_set_option(name.strip().encode(), int(value)), 'PASSL_OPTIONS %s' % kv)
-            from . import config
-            config.mirror_library_option(name.strip(), int(value))      # (wgrad_halo: one switch, two readers)
-        # the library reads PASSL_WGRAD_HALO itself; an explicit Python-side value (config.set_flag before load) wins
-        from . import config
-        if 'wgrad_halo' not in os.environ.get('PASSL_OPTIONS', ''):
-            check(lib.passl_hip_set_option(b'wgrad_halo', int(config.wgrad_halo())), 'set_option wgrad_halo')
+            set_option(name.strip(), int(value))
     return lib
 
 
@@ -230,6 +228,13 @@ def set_option(name, value):
     check(load().passl_hip_set_option(name.encode(), int(value)), 'set_option %s' % name)
     from . import config
     config.mirror_library_option(name, int(value))
+
+
+def get_option(name):
+    """The library's current value of a tuning option (passl_hip_get_option)."""
+    v = c_i()
+    check(load().passl_hip_get_option(name.encode(), C.byref(v)), 'get_option %s' % name)
+    return v.value
 
 
 def check(rc, what=''):

@@ -36,8 +36,8 @@ def test_every_declared_symbol_is_exported_and_bound(lib):
     assert sorted(L.SIGNATURES) == syms, 'lib.py binds symbols the header does not declare'
 
 
-def test_abi_version_and_strerror(lib):
-    assert lib.passl_hip_abi_version() == L.ABI_VERSION == 15
+def test_abi_version_16_and_strerror(lib):
+    assert lib.passl_hip_abi_version() == L.ABI_VERSION == 16
     assert ('#define PASSL_HIP_ABI_VERSION %d' % L.ABI_VERSION) in open(HEADER).read()
     assert b'invalid' in lib.passl_hip_strerror(-1)
     assert lib.passl_hip_strerror(0) == b'ok'

@@ -14,7 +14,7 @@
 //   tools/kbench fintime                    ... and their times, alone and next to a stream that loads the memory system
 //   tools/kbench finstress [iters=N]        ... and the multi-segment hand-off under load: every result bit-identical run to run
 //   tools/kbench poolcheck | pooltime       the stem's fused BatchNorm + ReLU + max-pool backward: second form == first form; times
-//   tools/kbench vtime                      the four epilogue variants of the K = 64 / 128 1x1 layers (PASSL_IGEMM_LEAN=1|2 to compare)
+//   tools/kbench vtime                      the four epilogue variants of the K = 64 / 128 1x1 layers (igemm_lean=0 to compare)
 //   tools/kbench ablate                     the register-staged kernel's debug switches on the 1x1 shapes
 //   tools/kbench sweep cfg [cfg ...]        cfg = "name=value,name=value": check + time the 3x3 shapes under each
 //   name=value pairs are passl_hip_set_option() calls made before anything runs.
@@ -867,7 +867,7 @@ static int run_sweep(int n, char** cfgs) {
 }
 
 // vtime: the four epilogue variants (ReLU, fused statistics, residual + ReLU, BatchNorm-backward) of the K = 64 1x1
-// layers at N = 256 — the launches the 4-workgroup form of the register-staged kernel takes (PASSL_IGEMM_LEAN).
+// layers at N = 256 — the launches the 4-workgroup form of the register-staged kernel takes (option igemm_lean).
 static int run_vtime() {
   const Shape shapes[] = {kR50[6], {256, 64, 64, 1, 1, 56, "64->64 k1 @56", 1}, kR50[8]};
   Buffers B;
@@ -907,28 +907,26 @@ static int run_vtime() {
   return 0;
 }
 
-// ablate: the register-staged kernel's debug switches (PASSL_IGEMM_DBG: 2 = return before the epilogue, 4 = no A
+// ablate: the register-staged kernel's debug switches (option igemm_dbg: 2 = return before the epilogue, 4 = no A
 // loads, 8 = no MFMAs) on the 1x1 shapes it serves: what a tile's time is made of.
 static int run_ablate() {
-  setenv("PASSL_IGEMM_DBG_DYNAMIC", "1", 1);
   const int sets[] = {0, 16, 16 | 32, 2, 8, 4, 2 | 8, 2 | 4 | 8};
   const Shape shapes[] = {kR50[6], kR50[7], kR50[8], kR50[10], {256, 64, 64, 1, 1, 56, "64->64 k1 @56", 1}};
   Buffers B;
-  printf("%-22s", "PASSL_IGEMM_DBG =");
+  printf("%-22s", "igemm_dbg =");
   for (int v : sets) printf(" %8d", v);
   printf("   (us, with fused statistics; 16 no statistics reduction / slab, 32 no statistics arithmetic, 2 no epilogue, 4 no A loads, 8 no MFMA)\n");
   for (const Shape& sh : shapes) {
     printf("%-22s", sh.note);
     for (int v : sets) {
-      char buf[16]; snprintf(buf, sizeof(buf), "%d", v);
-      setenv("PASSL_IGEMM_DBG", buf, 1);
+      if (passl_hip_set_option("igemm_dbg", v) != PASSL_OK) { printf("igemm_dbg=%d refused\n", v); return 1; }
       int used = -1;
       const float t = time_shape(sh, true, B, 20, &used);
       printf(" %8.1f", t);
     }
     printf("\n");
   }
-  setenv("PASSL_IGEMM_DBG", "0", 1);
+  passl_hip_set_option("igemm_dbg", 0);
   return 0;
 }
 
