@@ -591,6 +591,31 @@ int passl_hip_adamw(float* p, const float* g, float* m, float* v, int64_t n, flo
 int passl_hip_adamw_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, float beta1,
                         float beta2, float epsilon, float weight_decay, float grad_scale, passl_stream_t stream);
 
+/* ---------------------------------------------------------------- stochastic depth
+ * Reference: class DropPath / drop_path(), passl_v110/modeling/backbones/mae.py:32-50; the ladder
+ * linspace(0, drop_path_rate, depth) :234; the two uses per Block :186-187.  Token rows [B*T][C] in `dtype`, sample b
+ * owns rows b*T .. (b+1)*T-1; C % 8 == 0. */
+
+/* The keep table of one forward pass (paddle.rand + floor of drop_path(), mae.py:44-46, for every DropPath of the
+ * model in one launch): keep[slot][b] = (keep_prob[slot] + u >= 1.0f) ? 1 : 0, the sum rounded to fp32, with
+ * u = float(x0 >> 8) * 2^-24 and x0 the first output word of Philox4x32-10 on counter (b, slot, step_lo32, step_hi32),
+ * key (seed_lo32, seed_hi32); seed and *step taken as unsigned 64-bit patterns.  keep_prob [slots] is device memory
+ * (>= 1: always kept).  Every element uses the value *step (device, 8-byte aligned) had when the launch began; the
+ * launch leaves *step + 1 behind.  No argument varies from step to step: a step plan replays the launch as recorded
+ * and still draws a new table.  slots * B <= 2^24. */
+int passl_hip_drop_path_draw(float* keep, const float* keep_prob, int slots, int B, int64_t seed, int64_t* step,
+                             passl_stream_t stream);
+/* out = residual + keep[b] * (branch / keep_prob): `x + self.drop_path(f(norm(x)))`, mae.py:186-187, with
+ * drop_path() = x.divide(keep_prob) * random_tensor :47.  fp32 arithmetic, IEEE division, one rounding to `dtype`.
+ * Rows of a dropped sample (keep[b] == 0) are copied from residual; branch is not read for them.  keep: one row [B] of
+ * the table above; 0 < keep_prob <= 1. */
+int passl_hip_drop_path_add(const void* branch, const void* residual, const float* keep, float keep_prob, void* out,
+                            int B, int T, int C, int dtype, passl_stream_t stream);
+/* Its backward: dbranch = keep[b] * (dy / keep_prob); zeros for a dropped sample, dy not read.  The residual's gradient
+ * is dy itself. */
+int passl_hip_drop_path_bwd(const void* dy, const float* keep, float keep_prob, void* dbranch, int B, int T, int C,
+                            int dtype, passl_stream_t stream);
+
 /* ---------------------------------------------------------------- measurement hooks */
 
 /* When enabled, every passl_hip_conv_igemm / passl_hip_conv_wgrad launch is bracketed by HIP

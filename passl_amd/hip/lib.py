@@ -153,6 +153,9 @@ SIGNATURES = {
     'passl_hip_patchify': (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
     'passl_hip_mae_loss_fwd': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_l, c_p]),
     'passl_hip_mae_loss_bwd': (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p]),
+    'passl_hip_drop_path_draw': (c_i, [c_p, c_p, c_i, c_i, c_l, c_p, c_p]),
+    'passl_hip_drop_path_add': (c_i, [c_p, c_p, c_p, c_f, c_p, c_i, c_i, c_i, c_i, c_p]),
+    'passl_hip_drop_path_bwd': (c_i, [c_p, c_p, c_f, c_p, c_i, c_i, c_i, c_i, c_p]),
     'passl_hip_adamw': (c_i, [c_p, c_p, c_p, c_p, c_l, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_p]),
     'passl_hip_adamw_dev': (c_i, [c_p, c_p, c_p, c_p, c_l, c_p, c_f, c_f, c_f, c_f, c_f, c_p]),
     'passl_hip_cosine_loss_fwd': (c_i, [c_p, c_p, c_i, c_i, c_f, c_p, c_p, c_p]),

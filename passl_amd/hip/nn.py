@@ -783,6 +783,30 @@ class LayerNorm(Layer):
         return _LayerNormFn.apply(x, self.weight, self.bias, self)
 
 
+class _DropPathAddFn(Function):
+    """residual + keep_row[b] * (branch / keep_prob): the residual add of a block under stochastic depth
+    (csrc/drop_path.hip).  Backward returns (dbranch, dy): the second goes back into LayerNorm.fork's ``dres`` exactly
+    as the residual gradient of the fused GEMM epilogue does."""
+
+    @staticmethod
+    def forward(ctx, branch, residual, keep_row, keep_prob, B, T):
+        ctx.save_for_backward(keep_row)
+        ctx.args = (keep_prob, B, T)
+        return ops.drop_path_add(branch.contiguous(), residual.contiguous(), keep_row, keep_prob, B, T)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (keep_row,) = ctx.saved_tensors
+        keep_prob, B, T = ctx.args
+        dy = dy.contiguous()
+        return ops.drop_path_bwd(dy, keep_row, keep_prob, B, T), dy, None, None, None, None
+
+
+def drop_path_add(branch, residual, keep_row, keep_prob, B, T):
+    """keep_row: fp32 [B] on the device, 1 = sample kept, 0 = dropped (one row of the model's keep table)."""
+    return _DropPathAddFn.apply(branch, residual, keep_row, keep_prob, B, T)
+
+
 class _GeluFn(Function):
     @staticmethod
     def forward(ctx, x):

@@ -805,6 +805,36 @@ def patchify(img, p, dtype):
     return out
 
 
+# ------------------------------------------------------------------ stochastic depth (csrc/drop_path.hip)
+def drop_path_draw(keep, keep_prob, seed, step):
+    """One launch: keep [slots, B] fp32 <- 0 / 1 from Philox4x32-10 on (b, slot, *step) keyed by ``seed`` (a Python int,
+    its low 64 bits are used); ``step`` is a device int64 [1] that the launch reads and advances by one."""
+    slots, B = keep.shape
+    seed &= (1 << 64) - 1
+    if seed >= 1 << 63:
+        seed -= 1 << 64                                   # the same 64-bit pattern as a signed argument
+    L.check(_lib().passl_hip_drop_path_draw(L.ptr(keep), L.ptr(keep_prob), slots, B, seed, L.ptr(step), L.stream()),
+            'drop_path_draw')
+    return keep
+
+
+def drop_path_add(branch, residual, keep_row, keep_prob, B, T):
+    """residual + keep_row[b] * (branch / keep_prob) over rows [B*T, C]; keep_row: fp32 [B] on the device."""
+    Cc = branch.shape[-1]
+    out = torch.empty_like(branch)
+    L.check(_lib().passl_hip_drop_path_add(L.ptr(branch), L.ptr(residual), L.ptr(keep_row), keep_prob, L.ptr(out),
+                                           B, T, Cc, L.dt(branch), L.stream()), 'drop_path_add')
+    return out
+
+
+def drop_path_bwd(dy, keep_row, keep_prob, B, T):
+    Cc = dy.shape[-1]
+    dbranch = torch.empty_like(dy)
+    L.check(_lib().passl_hip_drop_path_bwd(L.ptr(dy), L.ptr(keep_row), keep_prob, L.ptr(dbranch), B, T, Cc,
+                                           L.dt(dy), L.stream()), 'drop_path_bwd')
+    return dbranch
+
+
 def mae_loss_fwd(img, pred, mask, p, norm_pix, denom):
     B, Cc, H, W = img.shape
     loss = torch.empty(1, dtype=torch.float32, device=img.device)

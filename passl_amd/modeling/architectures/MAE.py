@@ -53,7 +53,9 @@ class MAE_FINETUNE(nn.Layer):
     """Fine-tuning wrapper — reference passl_v110/modeling/architectures/MAE.py:58-94: ``train_iter(img, label)`` =
     backbone -> head -> ``head.loss`` (loss / acc1 / acc5); ``extract`` returns the pooled features.  The reference
     routes ``mode='test'`` to a ``test_iter`` it never defines (MAE.py:88-89); here it returns the class scores like
-    Classification.test_iter.  Backbone and head share one trainable arena (AdamW over flat buffers, DP reducer)."""
+    Classification.test_iter.  Backbone and head share one trainable arena (AdamW over flat buffers, DP reducer).
+    With ``architecture.drop_path_rate`` the backbone trains with stochastic depth (backbones/mae.py); the wrapper stays
+    eager (not ``graph_safe``: the pooling backward launches framework kernels)."""
 
     def __init__(self, architecture=None, head=None):
         super().__init__()
@@ -70,13 +72,15 @@ class MAE_FINETUNE(nn.Layer):
     def sync_runtime_state(self):
         self.arena_q.refresh()
 
-    def backbone_forward(self, x):
-        return self.backbone(x)
+    def backbone_forward(self, x, drop_path_keep=None):
+        return self.backbone(x) if drop_path_keep is None else self.backbone(x, drop_path_keep=drop_path_keep)
 
     def train_iter(self, *inputs, **kwargs):
+        # drop_path_keep= (tests, like noise= of MAE_PRETRAIN): the stochastic-depth keep table [2 * depth, B] to use
+        # instead of drawing one
         img, label = inputs
         self.arena_q.refresh()
-        outs = self.head(self.backbone_forward(img))
+        outs = self.head(self.backbone_forward(img, kwargs.get('drop_path_keep', None)))
         return self.head.loss(outs, label)
 
     def test_iter(self, *inputs, **kwargs):

@@ -9,10 +9,14 @@ attention / token gather-unshuffle / patchify / masked-patch loss are HIP kernel
 (csrc/vit.hip, csrc/attention.hip).  ``pos_embed`` / ``decoder_pos_embed`` are fixed sin-cos tables
 (reference: parameters with stop_gradient=True) kept as buffers under the same state_dict keys.
 The per-sample noise of random_masking comes from ``torch.rand`` on the device (``noise=`` lets
-tests inject the reference's draw); the argsort pair is replaced by a rank kernel."""
+tests inject the reference's draw); the argsort pair is replaced by a rank kernel.
+Stochastic depth of the fine-tuning ViT (``drop_path_rate``): one device-side Philox draw per forward pass fills a keep
+table, and the residual add of a block that can drop runs in csrc/drop_path.hip instead of the GEMM epilogue."""
 import math
+import os
 from functools import partial
 
+import numpy as np
 import torch
 import torch.nn as tnn
 from torch.autograd import Function
@@ -117,19 +121,38 @@ class Block(nn.Layer):
     def __init__(self, dim, num_heads, mlp_ratio=4., qkv_bias=False, drop=0., attn_drop=0., drop_path=0.,
                  act_layer=nn.GELU, norm_layer=nn.LayerNorm):
         super().__init__()
-        assert drop_path == 0., 'stochastic depth is not used by the MAE pre-training recipe'
+        # reference: DropPath(drop_path) if drop_path > 0. else Identity() (a layer without state); here the rate itself
+        # and keep_prob = float32(1 - p), the value drop_path() turns into a tensor and divides by (mae.py:36-40)
+        drop_path = float(drop_path)
+        if not 0. <= drop_path < 1.:
+            raise ValueError('drop_path must be in [0, 1), got %r' % drop_path)
+        self.drop_path = drop_path
+        self.keep_prob = float(np.float32(1.0) - np.float32(drop_path))
         self.norm1 = norm_layer(dim)
         self.attn = Attention(dim, num_heads=num_heads, qkv_bias=qkv_bias, attn_drop=attn_drop, proj_drop=drop)
         self.norm2 = norm_layer(dim)
         self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio), act_layer=act_layer, drop=drop)
 
-    def forward(self, x, B, T):
+    def forward(self, x, B, T, keep=None):
         # x + attn(norm1(x)) and x + mlp(norm2(x)): the add runs in the epilogue of proj / fc2, the
         # fork's gradient add inside the LayerNorm backward kernel (nn.LayerNorm.fork)
+        if self.drop_path > 0. and self.training:
+            return self._forward_drop_path(x, B, T, keep)
         h, xr = self.norm1.fork(x)
         x = self.attn(h, B, T, residual=xr)
         h, xr = self.norm2.fork(x)
         return self.mlp(h, residual=xr)
+
+    def _forward_drop_path(self, x, B, T, keep):
+        # x + drop_path(f(norm(x))) (mae.py:186-187): the factor is per sample, the epilogue's are per column, so the
+        # branch's last Linear runs without a residual and the add is a pass of its own.  keep: fp32 [2, B] on the
+        # device (row 0 the attention branch, row 1 the MLP branch), 1 = kept
+        if keep is None:
+            raise RuntimeError('Block(drop_path=%g) in training mode needs its two rows of the keep table' % self.drop_path)
+        h, xr = self.norm1.fork(x)
+        x = nn.drop_path_add(self.attn(h, B, T), xr, keep[0], self.keep_prob, B, T)
+        h, xr = self.norm2.fork(x)
+        return nn.drop_path_add(self.mlp(h), xr, keep[1], self.keep_prob, B, T)
 
 
 class _GatherFn(Function):
@@ -304,17 +327,34 @@ class _PatchMeanFn(Function):
         return dx.view(B * (L + 1), D), None, None, None
 
 
+def _process_rank():
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized():
+        return dist.get_rank()
+    return int(os.environ.get('RANK', 0))
+
+
 class VisionTransformer(nn.Layer):
     """The fine-tuning ViT of the v110 tree (passl_v110/modeling/backbones/mae.py:190-277): learnable ``cls_token`` /
     ``pos_embed`` (trunc-normal 0.02), pre-norm blocks, final LayerNorm, output = the class token's row.  Same kernels as
-    the pre-training encoder above; dropout / stochastic depth are not built (0 in the yaml's defaults)."""
+    the pre-training encoder above.  ``drop_path_rate`` is stochastic depth with the reference's ladder
+    ``linspace(0, rate, depth)`` (:234); element-wise dropout (``drop_rate`` / ``attn_drop_rate``) is not built.
+
+    Stochastic depth state (plain attributes: not in ``state_dict()``, not broadcast by ``param_sync``): the keep table
+    [2 * depth, B] per batch size (row 2i = attention branch of block i, row 2i + 1 = its MLP branch), the device vector
+    of keep probabilities (1.0 for block 0), a device int64 step counter and the seed.  One
+    ``passl_hip_drop_path_draw`` launch per training forward fills the table from (seed, counter) and advances the
+    counter on the device.  The seed comes from torch's global CPU generator at construction plus the process rank, so
+    ``torch.manual_seed(seed + rank)`` reproduces a run and data-parallel ranks draw different masks."""
 
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=1000, embed_dim=768, depth=12,
                  num_heads=12, mlp_ratio=4., qkv_bias=True, drop_rate=0., attn_drop_rate=0., drop_path_rate=0.,
                  embed_layer=PatchEmbed, norm_layer=None, act_layer=None, weight_init=''):
         super().__init__()
-        if drop_rate or attn_drop_rate or drop_path_rate:
-            raise NotImplementedError('dropout / stochastic depth are not built on the HIP path')
+        if drop_rate or attn_drop_rate:
+            raise NotImplementedError('element-wise dropout is not built on the HIP path')
+        if not 0. <= drop_path_rate < 1.:
+            raise ValueError('drop_path_rate must be in [0, 1), got %r' % (drop_path_rate,))
         dev = config.get_device()
         self.num_classes = num_classes
         self.num_features = self.embed_dim = embed_dim
@@ -328,10 +368,19 @@ class VisionTransformer(nn.Layer):
                                       % (num_patches + 1, embed_dim / float(num_heads)))
         self.cls_token = tnn.Parameter(torch.zeros(1, 1, embed_dim, device=dev))
         self.pos_embed = tnn.Parameter(torch.zeros(1, num_patches + 1, embed_dim, device=dev))
+        # dpr = [x.item() for x in paddle.linspace(0, drop_path_rate, depth)]: a float32 ladder
+        dpr = [x.item() for x in torch.linspace(0, drop_path_rate, depth, dtype=torch.float32)]
         self.blocks = tnn.Sequential(*[Block(embed_dim, num_heads, mlp_ratio, qkv_bias=qkv_bias, norm_layer=norm_layer,
-                                             act_layer=act_layer) for _ in range(depth)])
+                                             act_layer=act_layer, drop_path=dpr[i]) for i in range(depth)])
         self.norm = norm_layer(embed_dim)
         self._ids = {}
+        self.drop_path_rate = float(drop_path_rate)
+        self._dp_tables = {}                                   # batch size -> keep table [2 * depth, B]
+        self._dp_keep_prob = self._dp_step = None              # device state, made on first use
+        self._dp_seed = self._dp_step0 = 0
+        if self.drop_path_rate > 0.:
+            seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+            self.set_drop_path_seed(seed + _process_rank())
         trunc_normal_(self.cls_token, std=0.02)
         trunc_normal_(self.pos_embed, std=0.02)
         with torch.no_grad():
@@ -352,23 +401,66 @@ class VisionTransformer(nn.Layer):
                               (torch.arange(B, dtype=torch.int32, device=device) * (L + 1)).contiguous())
         return self._ids[key]
 
-    def _tokens(self, x):
+    # -- stochastic depth ------------------------------------------------------------------------------------------
+    def set_drop_path_seed(self, seed, step=0):
+        """Key of the Philox draw and the value of the step counter (tests; a resumed run restarts at step 0)."""
+        self._dp_seed = int(seed) & ((1 << 64) - 1)
+        self._dp_step0 = int(step)
+        if self._dp_step is not None:
+            self._dp_step.fill_(self._dp_step0 - (1 << 64) if self._dp_step0 >= 1 << 63 else self._dp_step0)
+
+    def drop_path_step(self):
+        """The step counter = the number of draws since set_drop_path_seed (reads the device: synchronises)."""
+        return self._dp_step0 if self._dp_step is None else int(self._dp_step.item()) & ((1 << 64) - 1)
+
+    def drop_path_table(self, B):
+        """The keep table [2 * depth, B] the last training forward of batch size B used (None before the first)."""
+        return self._dp_tables.get(B)
+
+    def _drop_path_keep(self, B, device, given=None):
+        """-> the keep table of this forward pass, or None when nothing can drop (eval mode, rate 0)."""
+        if not (self.training and self.drop_path_rate > 0.):
+            if given is not None:
+                raise ValueError('drop_path_keep= needs a model in training mode built with drop_path_rate > 0')
+            return None
+        slots = 2 * len(self.blocks)
+        if given is not None:
+            if tuple(given.shape) != (slots, B):
+                raise ValueError('drop_path_keep must be [2 * depth, B] = [%d, %d], got %s'
+                                 % (slots, B, tuple(given.shape)))
+            return given.to(device=device, dtype=torch.float32).contiguous()
+        if self._dp_step is None:
+            self._dp_keep_prob = torch.tensor([blk.keep_prob for blk in self.blocks for _ in range(2)],
+                                              dtype=torch.float32, device=device)
+            self._dp_step = torch.zeros(1, dtype=torch.int64, device=device)
+            self.set_drop_path_seed(self._dp_seed, self._dp_step0)
+        keep = self._dp_tables.get(B)
+        if keep is None:
+            keep = self._dp_tables[B] = torch.empty(slots, B, dtype=torch.float32, device=device)
+        return ops.drop_path_draw(keep, self._dp_keep_prob, self._dp_seed, self._dp_step)
+
+    def _tokens(self, x, drop_path_keep=None):
         from .vision_transformer import _ClsPosFn
         B = x.shape[0]
         L = self.patch_embed.num_patches
+        keep = self._drop_path_keep(B, x.device, drop_path_keep)
         x = self.patch_embed(x)                                           # [B*L, D]
         ids, cls_rows = self._token_ids(B, L, x.device)
         x = _ClsPosFn.apply(x, self.cls_token, self.pos_embed, ids, B, L)     # concat(cls, x) + pos_embed
-        for blk in self.blocks:
-            x = blk(x, B, L + 1)
+        if keep is None:
+            for blk in self.blocks:
+                x = blk(x, B, L + 1)
+        else:
+            for i, blk in enumerate(self.blocks):
+                x = blk(x, B, L + 1, keep[2 * i:2 * i + 2])
         return x, cls_rows, B, L
 
-    def forward_features(self, x):
-        x, cls_rows, _B, _L = self._tokens(x)
+    def forward_features(self, x, drop_path_keep=None):
+        x, cls_rows, _B, _L = self._tokens(x, drop_path_keep)
         return self.norm(nn.gather_rows(x, cls_rows))                     # norm(x)[:, 0]: LayerNorm is per token
 
-    def forward(self, x):
-        return self.forward_features(x)
+    def forward(self, x, drop_path_keep=None):
+        return self.forward_features(x, drop_path_keep)
 
 
 @BACKBONES.register()
@@ -383,8 +475,8 @@ class MAE_ViT(VisionTransformer):
             self.fc_norm = nn.LayerNorm(kwargs['embed_dim'], epsilon=1e-6)
             del self.norm                                                  # remove the original norm
 
-    def forward_features(self, x):
-        x, cls_rows, B, L = self._tokens(x)
+    def forward_features(self, x, drop_path_keep=None):
+        x, cls_rows, B, L = self._tokens(x, drop_path_keep)
         if self.global_pool:
             return self.fc_norm(_PatchMeanFn.apply(x, cls_rows, B, L))
         return self.norm(nn.gather_rows(x, cls_rows))
