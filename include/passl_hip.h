@@ -616,6 +616,38 @@ int passl_hip_drop_path_add(const void* branch, const void* residual, const floa
 int passl_hip_drop_path_bwd(const void* dy, const float* keep, float keep_prob, void* dbranch, int B, int T, int C,
                             int dtype, passl_stream_t stream);
 
+/* ---------------------------------------------------------------- mixup / cutmix and soft-target cross-entropy
+ * Reference: class Mixup, passl_v110/datasets/preprocess/mixup.py:108-276 (the reference mixes on the host, in numpy or
+ * through the framework's CPU tensors); SoftTargetCrossEntropy, tasks/ssl/mae/util/loss.py:44-47. */
+
+/* Mixup._mix_batch (mixup.py:248-264) on a resident batch: x, out fp32 NCHW [B,C,H,W], OUT OF PLACE (x is not written;
+ * x == out is refused).  The partner of sample b is B-1-b (x.flip(0)); the middle sample of an odd B is its own partner.
+ *   mode 0 (mixup, :261-263): out = fl(fl(x * lam) + fl(x' * one_minus_lam)), fp32, two separately rounded products
+ *     and a rounded sum (no FMA).  The caller passes float(lam) and float(1.0 - lam), the subtraction done in double.
+ *   mode 1 (CutMix, :259): out = x' in rows [yl, yh) x columns [xl, xh) of every channel, x elsewhere; lam and
+ *     one_minus_lam are ignored.  An empty box copies x.
+ * The box must satisfy 0 <= yl <= yh <= H, 0 <= xl <= xh <= W in both modes.  One lane handles the same elements of a
+ * sample and of its partner, so a launch reads and writes each byte of the batch once.  16-byte accesses when
+ * C*H*W % 4 == 0 and both pointers are 16-byte aligned, single floats otherwise. */
+int passl_hip_batch_mix(const float* x, float* out, int B, int C, int H, int W, float lam, float one_minus_lam, int yl,
+                        int yh, int xl, int xh, int mode, passl_stream_t stream);
+/* mixup_target (mixup.py:29-37): labels int64 [N] -> target fp32 [N,C] (16-byte aligned),
+ * target[i] = lam * smooth(onehot(labels[i])) + (1 - lam) * smooth(onehot(labels[N-1-i])),
+ * smooth(v) = (1 - eps) * v + eps / C.  lam = 1: plain label smoothing; lam = 1, eps = 0: one-hot.  lam, eps in [0, 1].
+ * A label outside [0,C) makes every row that uses it NaN. */
+int passl_hip_mixup_target(const int64_t* labels, float* target, int N, int C, float lam, float eps,
+                           passl_stream_t stream);
+/* SoftTargetCrossEntropy (util/loss.py:44-47; passl/loss/celoss.py:48-49): scores, target fp32 [N,C] ->
+ * lse [N], tsum [N] (T_i = sum_j t_ij; both saved for the backward), out = {mean_i (lse_i T_i - sum_j t_ij s_ij),
+ * acc1 (%), acc5 (%)}.  Rows need not sum to one.  Accuracy is taken against argmax_j t_ij (lowest index on ties; the
+ * wrappers that accept mixup_fn do the same, architectures/ViTWrapper.py:91-108) by rank counting as in
+ * passl_hip_softmax_ce_fwd.  ws: 3 * N floats (per-row terms, summed in a fixed order). */
+int passl_hip_soft_ce_fwd(const float* scores, const float* target, int N, int C, float* lse, float* tsum, float* out,
+                          float* ws, int64_t ws_floats, passl_stream_t stream);
+/* dscores[i][j] = gloss/N * (exp(scores_ij - lse_i) * tsum_i - target_ij); gloss: device scalar. */
+int passl_hip_soft_ce_bwd(const float* scores, const float* target, const float* lse, const float* tsum,
+                          const float* gloss, int N, int C, float* dscores, passl_stream_t stream);
+
 /* ---------------------------------------------------------------- measurement hooks */
 
 /* When enabled, every passl_hip_conv_igemm / passl_hip_conv_wgrad launch is bracketed by HIP

@@ -14,9 +14,13 @@ def build_dataset(cfg):
 
 
 def build_dataloader(cfg, device):
-    """cfg = dataloader.train block: {loader, sampler, dataset}.  Returns (loader, mixup_fn)."""
+    """cfg = dataloader.train block: {loader, sampler, dataset}.  Returns (loader, mixup_fn): ``dataset.batch_transforms``
+    is popped as the reference does (builder.py:88-103) and built by preprocess.build_mixup — a Mixup when the block
+    mixes, else None.  The Trainer hands it to every model call; only the train block's is used."""
+    from .preprocess import build_mixup
     from .synthetic import SyntheticLoader
     ds_cfg = dict(cfg['dataset'])
+    mixup_cfg = ds_cfg.pop('batch_transforms', None)
     sampler = cfg.get('sampler', {})
     dataset = build_dataset(ds_cfg)
     loader = SyntheticLoader(dataset, batch_size=sampler.get('batch_size', 32), device=device,
@@ -25,4 +29,4 @@ def build_dataloader(cfg, device):
     if ring:
         from .synthetic import HostRingLoader
         loader = HostRingLoader(loader, ring=ring)       # batches move host -> device one step ahead of the step
-    return loader, None
+    return loader, build_mixup(mixup_cfg)

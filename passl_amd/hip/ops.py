@@ -835,6 +835,53 @@ def drop_path_bwd(dy, keep_row, keep_prob, B, T):
     return dbranch
 
 
+# ------------------------------------------------------------------ mixup / cutmix, soft targets (csrc/mixup.hip)
+def batch_mix(x, lam, box=None):
+    """Mixup._mix_batch on a resident fp32 NCHW batch, out of place (``x`` is not written); the partner of sample b is
+    B-1-b.  ``box`` None: mixup, fl(fl(x * f32(lam)) + fl(x.flip(0) * f32(1 - lam))).  ``box`` = (yl, yh, xl, xh): CutMix,
+    x.flip(0) inside the box.  lam and the box are host numbers (plain kernel arguments)."""
+    assert x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()
+    B, Cc, H, W = x.shape
+    out = torch.empty_like(x)
+    lam = float(lam)
+    yl, yh, xl, xh = (0, 0, 0, 0) if box is None else (int(v) for v in box)
+    L.check(_lib().passl_hip_batch_mix(L.ptr(x), L.ptr(out), B, Cc, H, W, lam, 1.0 - lam, yl, yh, xl, xh,
+                                       0 if box is None else 1, L.stream()), 'batch_mix')
+    return out
+
+
+def mixup_target(labels, num_classes, lam=1.0, eps=0.0):
+    """labels int64 [N] -> fp32 [N, num_classes]: lam * smooth(onehot(y)) + (1 - lam) * smooth(onehot(y.flip(0))),
+    smooth(v) = (1 - eps) v + eps / C.  lam = 1: plain label smoothing."""
+    assert labels.dtype == torch.int64 and labels.dim() == 1 and labels.is_contiguous()
+    N = labels.shape[0]
+    target = torch.empty(N, num_classes, dtype=torch.float32, device=labels.device)
+    L.check(_lib().passl_hip_mixup_target(L.ptr(labels), L.ptr(target), N, num_classes, float(lam), float(eps),
+                                          L.stream()), 'mixup_target')
+    return target
+
+
+def soft_ce_fwd(scores, target):
+    """scores, target fp32 [N,C] -> out[3] = (loss, acc1 %, acc5 % against argmax target), lse [N], tsum [N]."""
+    assert scores.shape == target.shape and target.dtype == torch.float32
+    N, Cc = scores.shape
+    lse = torch.empty(N, dtype=torch.float32, device=scores.device)
+    tsum = torch.empty(N, dtype=torch.float32, device=scores.device)
+    out = torch.empty(3, dtype=torch.float32, device=scores.device)
+    ws = workspace.get(3 * N, scores.device)
+    L.check(_lib().passl_hip_soft_ce_fwd(L.ptr(scores), L.ptr(target), N, Cc, L.ptr(lse), L.ptr(tsum), L.ptr(out),
+                                         L.ptr(ws), ws.numel(), L.stream()), 'soft_ce_fwd')
+    return out, lse, tsum
+
+
+def soft_ce_bwd(scores, target, lse, tsum, gloss):
+    N, Cc = scores.shape
+    ds = torch.empty_like(scores)
+    L.check(_lib().passl_hip_soft_ce_bwd(L.ptr(scores), L.ptr(target), L.ptr(lse), L.ptr(tsum), L.ptr(gloss), N, Cc,
+                                         L.ptr(ds), L.stream()), 'soft_ce_bwd')
+    return ds
+
+
 def mae_loss_fwd(img, pred, mask, p, norm_pix, denom):
     B, Cc, H, W = img.shape
     loss = torch.empty(1, dtype=torch.float32, device=img.device)

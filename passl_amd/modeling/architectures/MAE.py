@@ -55,7 +55,11 @@ class MAE_FINETUNE(nn.Layer):
     routes ``mode='test'`` to a ``test_iter`` it never defines (MAE.py:88-89); here it returns the class scores like
     Classification.test_iter.  Backbone and head share one trainable arena (AdamW over flat buffers, DP reducer).
     With ``architecture.drop_path_rate`` the backbone trains with stochastic depth (backbones/mae.py); the wrapper stays
-    eager (not ``graph_safe``: the pooling backward launches framework kernels)."""
+    eager (not ``graph_safe``: the pooling backward launches framework kernels).
+    ``mixup_fn=`` (the Trainer passes what build_dataloader built from ``dataset.batch_transforms``) mixes the batch and
+    turns the labels into a soft target before the forward when the model is training, the pattern of the reference's
+    ViTWrapper.py:64-68.  The reference's MAE_FINETUNE ignores the argument — its recipe mixes in the collate function
+    instead (tasks/ssl/mae/main_finetune.py:315-333).  ``test_iter`` never mixes."""
 
     def __init__(self, architecture=None, head=None):
         super().__init__()
@@ -79,6 +83,9 @@ class MAE_FINETUNE(nn.Layer):
         # drop_path_keep= (tests, like noise= of MAE_PRETRAIN): the stochastic-depth keep table [2 * depth, B] to use
         # instead of drawing one
         img, label = inputs
+        mixup_fn = kwargs.get('mixup_fn', None)
+        if mixup_fn is not None and self.training:
+            img, label = mixup_fn(img, label)
         self.arena_q.refresh()
         outs = self.head(self.backbone_forward(img, kwargs.get('drop_path_keep', None)))
         return self.head.loss(outs, label)

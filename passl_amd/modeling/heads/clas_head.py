@@ -30,6 +30,34 @@ class _SoftmaxCEFn(Function):
         return ops.softmax_ce_bwd(scores, lse, labels, gloss.contiguous().float()), None
 
 
+class _SoftCEFn(Function):
+    """Cross-entropy over a dense fp32 target [N, C] (mixup / cutmix / label smoothing): mean_i sum_j -t_ij log_softmax(s_i)_j
+    (csrc/mixup.hip), accuracies against argmax_j t_ij.  The target gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, scores, target):
+        ctx.set_materialize_grads(False)
+        scores = scores.contiguous()
+        target = target.contiguous()
+        out, lse, tsum = ops.soft_ce_fwd(scores, target)
+        ctx.save_for_backward(scores, target, lse, tsum)
+        loss, acc1, acc5 = out[0:1], out[1:2], out[2:3]
+        ctx.mark_non_differentiable(acc1, acc5)
+        return loss, acc1, acc5
+
+    @staticmethod
+    def backward(ctx, gloss, _g1, _g5):
+        scores, target, lse, tsum = ctx.saved_tensors
+        if gloss is None:
+            return None, None
+        return ops.soft_ce_bwd(scores, target, lse, tsum, gloss.contiguous().float()), None
+
+
+def is_soft_label(cls_score, labels):
+    """A floating [N, C] label is a soft target; anything else is integer class ids."""
+    return labels.is_floating_point() and labels.dim() == 2 and labels.shape == cls_score.shape
+
+
 def accuracy(output, target, topk=(1, 5)):
     """clas_head.py:58-72 for topk = (1, 5): percentages as 1-element tensors."""
     if tuple(topk) != (1, 5):
@@ -66,7 +94,10 @@ class ClasHead(nn.Layer):
 
     def loss(self, cls_score, labels):
         losses = dict()
-        loss, acc1, acc5 = _SoftmaxCEFn.apply(cls_score, labels.contiguous().long().view(-1))
+        if is_soft_label(cls_score, labels):               # mixup / cutmix target (datasets/preprocess/mixup.py)
+            loss, acc1, acc5 = _SoftCEFn.apply(cls_score, labels.float())
+        else:
+            loss, acc1, acc5 = _SoftmaxCEFn.apply(cls_score, labels.contiguous().long().view(-1))
         losses['loss'] = loss
         losses['acc1'], losses['acc5'] = acc1, acc5
         return losses
