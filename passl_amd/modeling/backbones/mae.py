@@ -2,7 +2,8 @@
 
 Constructor, registry name, sub-layer / state_dict names and the ``forward(imgs, mask_ratio)``
 -> ``(loss, pred, mask)`` contract are the reference's ``MAE`` (passl_v110/modeling/backbones/
-mae.py:318-564, twin of passl/models/mae.py:37-290); Mlp / Attention / Block follow :61-189.
+mae.py:318-564, twin of passl/models/mae.py:37-290); Mlp / Attention / Block / PatchEmbed and the token assembly are
+the shared ones of passl_amd/modules/vit.py (re-exported here under the reference's names).
 Execution: tokens are 2-D rows [B*T, C] in the compute dtype; every Linear is the implicit-GEMM
 kernel (bias, residual add in the epilogue; fp32 output for the pixel prediction), LayerNorm / GELU /
 attention / token gather-unshuffle / patchify / masked-patch loss are HIP kernels
@@ -12,167 +13,18 @@ The per-sample noise of random_masking comes from ``torch.rand`` on the device (
 tests inject the reference's draw); the argsort pair is replaced by a rank kernel.
 Stochastic depth of the fine-tuning ViT (``drop_path_rate``): one device-side Philox draw per forward pass fills a keep
 table, and the residual add of a block that can drop runs in csrc/drop_path.hip instead of the GEMM epilogue."""
-import math
 import os
 from functools import partial
 
-import numpy as np
 import torch
 import torch.nn as tnn
 from torch.autograd import Function
 
-from ...hip import config, nn, ops, plan as P
+from ...hip import config, nn, ops
 from ...modules.get_sincos_pe import get_2d_sincos_pos_embed
+from ...modules.vit import (Attention, Block, Identity, Mlp, PatchEmbed, ViTTrunk, _TokensFn,      # noqa: F401
+                            alias_matrix_param, conv_default_normal_, to_2tuple, trunc_normal_, xavier_uniform_)
 from .builder import BACKBONES
-
-
-@torch.no_grad()
-def xavier_uniform_(w, fan_in, fan_out):
-    a = math.sqrt(6.0 / (fan_in + fan_out))
-    w.copy_((torch.rand(w.shape) * 2 - 1) * a)
-
-
-@torch.no_grad()
-def trunc_normal_(w, std=0.02):
-    # paddle TruncatedNormal(std): N(0, std) re-sampled (not wrapped) into [-2 std, 2 std]
-    t = torch.empty(w.shape)
-    torch.nn.init.trunc_normal_(t, mean=0.0, std=std, a=-2.0 * std, b=2.0 * std)
-    w.copy_(t)
-
-
-class Identity(nn.Layer):
-    def forward(self, x):
-        return x
-
-
-class Mlp(nn.Layer):
-    def __init__(self, in_features, hidden_features=None, out_features=None, act_layer=nn.GELU, drop=0.):
-        super().__init__()
-        assert drop == 0., 'dropout is not used by the MAE pre-training recipe'
-        out_features = out_features or in_features
-        hidden_features = hidden_features or in_features
-        self.fc1 = nn.Linear(in_features, hidden_features)
-        self.act = act_layer()
-        self.fc2 = nn.Linear(hidden_features, out_features)
-
-    def forward(self, x, residual=None):
-        return self.fc2(self.act(self.fc1(x)), residual=residual)
-
-
-class _PatchProj(nn.Layer):
-    """The 16x16/stride-16 patch-embedding convolution as a GEMM over patchified rows.  ``weight`` is
-    logically [embed_dim, in_chans, p, p] (reference layout) and physically [embed_dim][p][p][in_chans]
-    = the K-order the patchify kernel writes."""
-    krsc_weight = True
-    no_dgrad = True           # the image needs no gradient
-
-    def __init__(self, in_chans, embed_dim, patch, bias=True):
-        super().__init__()
-        dev = config.get_device()
-        self.patch, self.in_chans, self.out_features = patch, in_chans, embed_dim
-        self.in_features = in_chans * patch * patch
-        self.geom = P.ConvGeom(self.in_features, embed_dim, 1, 1, 0)
-        self.weight = tnn.Parameter(torch.empty(embed_dim, in_chans, patch, patch, device=dev))
-        self.bias = tnn.Parameter(torch.zeros(embed_dim, device=dev)) if bias else None
-        self._rt = None
-        self._plans = {}
-
-    _plan = nn.Linear._plan
-
-    def forward(self, rows):
-        return nn._LinearFn.apply(rows, self.weight, self.bias, self, False, False, None)
-
-
-class PatchEmbed(nn.Layer):
-    def __init__(self, img_size=224, patch_size=16, in_chans=3, embed_dim=768, norm_layer=None, flatten=True):
-        super().__init__()
-        self.img_size = (img_size, img_size)
-        self.patch_size = (patch_size, patch_size)
-        self.grid_size = (img_size // patch_size, img_size // patch_size)
-        self.num_patches = self.grid_size[0] * self.grid_size[1]
-        self.proj = _PatchProj(in_chans, embed_dim, patch_size)
-        self.norm = norm_layer(embed_dim) if norm_layer else Identity()
-
-    def forward(self, x):
-        B, C, H, W = x.shape
-        assert H == self.img_size[0], f"Input image height ({H}) doesn't match model ({self.img_size[0]})."
-        assert W == self.img_size[1], f"Input image width ({W}) doesn't match model ({self.img_size[1]})."
-        dtype = nn._need_rt(self.proj).arena.dtype
-        rows = ops.patchify(x.contiguous().float(), self.patch_size[0], dtype)
-        return self.norm(self.proj(rows))                    # [B*L, embed_dim]
-
-
-class Attention(nn.Layer):
-    def __init__(self, dim, num_heads=8, qkv_bias=False, attn_drop=0., proj_drop=0.):
-        super().__init__()
-        assert attn_drop == 0. and proj_drop == 0.
-        self.num_heads = num_heads
-        self.head_dim = dim // num_heads
-        self.scale = self.head_dim ** -0.5
-        self.qkv = nn.Linear(dim, dim * 3, bias_attr=None if qkv_bias else False)
-        self.proj = nn.Linear(dim, dim)
-
-    def forward(self, x, B, T, residual=None):
-        a = nn.attention(self.qkv(x), B, T, self.num_heads, self.head_dim, self.scale)
-        return self.proj(a, residual=residual)
-
-
-class Block(nn.Layer):
-    def __init__(self, dim, num_heads, mlp_ratio=4., qkv_bias=False, drop=0., attn_drop=0., drop_path=0.,
-                 act_layer=nn.GELU, norm_layer=nn.LayerNorm):
-        super().__init__()
-        # reference: DropPath(drop_path) if drop_path > 0. else Identity() (a layer without state); here the rate itself
-        # and keep_prob = float32(1 - p), the value drop_path() turns into a tensor and divides by (mae.py:36-40)
-        drop_path = float(drop_path)
-        if not 0. <= drop_path < 1.:
-            raise ValueError('drop_path must be in [0, 1), got %r' % drop_path)
-        self.drop_path = drop_path
-        self.keep_prob = float(np.float32(1.0) - np.float32(drop_path))
-        self.norm1 = norm_layer(dim)
-        self.attn = Attention(dim, num_heads=num_heads, qkv_bias=qkv_bias, attn_drop=attn_drop, proj_drop=drop)
-        self.norm2 = norm_layer(dim)
-        self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio), act_layer=act_layer, drop=drop)
-
-    def forward(self, x, B, T, keep=None):
-        # x + attn(norm1(x)) and x + mlp(norm2(x)): the add runs in the epilogue of proj / fc2, the
-        # fork's gradient add inside the LayerNorm backward kernel (nn.LayerNorm.fork)
-        if self.drop_path > 0. and self.training:
-            return self._forward_drop_path(x, B, T, keep)
-        h, xr = self.norm1.fork(x)
-        x = self.attn(h, B, T, residual=xr)
-        h, xr = self.norm2.fork(x)
-        return self.mlp(h, residual=xr)
-
-    def _forward_drop_path(self, x, B, T, keep):
-        # x + drop_path(f(norm(x))) (mae.py:186-187): the factor is per sample, the epilogue's are per column, so the
-        # branch's last Linear runs without a residual and the add is a pass of its own.  keep: fp32 [2, B] on the
-        # device (row 0 the attention branch, row 1 the MLP branch), 1 = kept
-        if keep is None:
-            raise RuntimeError('Block(drop_path=%g) in training mode needs its two rows of the keep table' % self.drop_path)
-        h, xr = self.norm1.fork(x)
-        x = nn.drop_path_add(self.attn(h, B, T), xr, keep[0], self.keep_prob, B, T)
-        h, xr = self.norm2.fork(x)
-        return nn.drop_path_add(self.mlp(h), xr, keep[1], self.keep_prob, B, T)
-
-
-class _GatherFn(Function):
-    @staticmethod
-    def forward(ctx, x, cls_token, pos, ids_keep, ids_restore, B, L):
-        ctx.save_for_backward(ids_restore)
-        ctx.cls, ctx.dims = cls_token, (B, L, ids_keep.shape[1])
-        nn.param_expect_grad(cls_token)
-        return ops.mae_gather(x, cls_token.detach().view(-1), pos.view(-1, pos.shape[-1]), ids_keep, B, L)
-
-    @staticmethod
-    def backward(ctx, dout):
-        (ids_restore,) = ctx.saved_tensors
-        B, L, K = ctx.dims
-        cls = ctx.cls
-        if cls.grad is None:
-            cls.grad = torch.zeros_like(cls)
-        dx = ops.mae_gather_bwd(dout.contiguous(), ids_restore, cls.grad, B, L, K)
-        nn.param_grad_ready(cls)
-        return dx, None, None, None, None, None, None
 
 
 class _UnshuffleFn(Function):
@@ -274,7 +126,7 @@ class MAE(nn.Layer):
         L = self.patch_embed.num_patches
         x = self.patch_embed(imgs)                                       # [B*L, D]
         ids_keep, ids_restore, mask, K = self.random_masking_ids(B, L, mask_ratio, noise)
-        x = _GatherFn.apply(x, self.cls_token, self.pos_embed, ids_keep, ids_restore, B, L)
+        x = _TokensFn.apply(x, self.cls_token, self.pos_embed, ids_keep, ids_restore, B, L)
         for blk in self.blocks:
             x = blk(x, B, K + 1)
         return self.norm(x), mask, (ids_keep, ids_restore)
@@ -334,7 +186,7 @@ def _process_rank():
     return int(os.environ.get('RANK', 0))
 
 
-class VisionTransformer(nn.Layer):
+class VisionTransformer(ViTTrunk):
     """The fine-tuning ViT of the v110 tree (passl_v110/modeling/backbones/mae.py:190-277): learnable ``cls_token`` /
     ``pos_embed`` (trunc-normal 0.02), pre-norm blocks, final LayerNorm, output = the class token's row.  Same kernels as
     the pre-training encoder above.  ``drop_path_rate`` is stochastic depth with the reference's ladder
@@ -362,10 +214,7 @@ class VisionTransformer(nn.Layer):
         act_layer = act_layer or nn.GELU
         self.patch_embed = embed_layer(img_size=img_size, patch_size=patch_size, in_chans=in_chans, embed_dim=embed_dim)
         num_patches = self.patch_embed.num_patches
-        if embed_dim % num_heads or embed_dim // num_heads not in ops.ATTENTION_HEAD_DIMS or \
-                num_patches + 1 > ops.ATTENTION_MAX_TOKENS:
-            raise NotImplementedError('%d tokens x head dimension %s is outside the HIP attention kernels'
-                                      % (num_patches + 1, embed_dim / float(num_heads)))
+        self.check_attention_envelope(img_size, patch_size, embed_dim, num_heads, num_patches + 1)
         self.cls_token = tnn.Parameter(torch.zeros(1, 1, embed_dim, device=dev))
         self.pos_embed = tnn.Parameter(torch.zeros(1, num_patches + 1, embed_dim, device=dev))
         # dpr = [x.item() for x in paddle.linspace(0, drop_path_rate, depth)]: a float32 ladder
@@ -373,7 +222,6 @@ class VisionTransformer(nn.Layer):
         self.blocks = tnn.Sequential(*[Block(embed_dim, num_heads, mlp_ratio, qkv_bias=qkv_bias, norm_layer=norm_layer,
                                              act_layer=act_layer, drop_path=dpr[i]) for i in range(depth)])
         self.norm = norm_layer(embed_dim)
-        self._ids = {}
         self.drop_path_rate = float(drop_path_rate)
         self._dp_tables = {}                                   # batch size -> keep table [2 * depth, B]
         self._dp_keep_prob = self._dp_step = None              # device state, made on first use
@@ -386,20 +234,12 @@ class VisionTransformer(nn.Layer):
         with torch.no_grad():
             # self.apply(self._init_weights): Linear trunc_normal(.02) / zero bias, LayerNorm (1, 0); the patch
             # convolution keeps nn.Conv2D's default [Paddle-semantics]: Normal(0, sqrt(2 / fan_in)), zero bias
-            w = self.patch_embed.proj.weight
-            w.copy_(torch.randn(w.shape) * math.sqrt(2.0 / (w.shape[1] * w.shape[2] * w.shape[3])))
+            conv_default_normal_(self.patch_embed.proj.weight)
             for m in self.modules():
                 if isinstance(m, nn.Linear):
                     trunc_normal_(m.weight, std=0.02)
                     if m.bias is not None:
                         m.bias.zero_()
-
-    def _token_ids(self, B, L, device):
-        key = (B, L)
-        if key not in self._ids:
-            self._ids[key] = (torch.arange(L, dtype=torch.int32, device=device).repeat(B, 1).contiguous(),
-                              (torch.arange(B, dtype=torch.int32, device=device) * (L + 1)).contiguous())
-        return self._ids[key]
 
     # -- stochastic depth ------------------------------------------------------------------------------------------
     def set_drop_path_seed(self, seed, step=0):
@@ -440,24 +280,13 @@ class VisionTransformer(nn.Layer):
         return ops.drop_path_draw(keep, self._dp_keep_prob, self._dp_seed, self._dp_step)
 
     def _tokens(self, x, drop_path_keep=None):
-        from .vision_transformer import _ClsPosFn
-        B = x.shape[0]
-        L = self.patch_embed.num_patches
-        keep = self._drop_path_keep(B, x.device, drop_path_keep)
-        x = self.patch_embed(x)                                           # [B*L, D]
-        ids, cls_rows = self._token_ids(B, L, x.device)
-        x = _ClsPosFn.apply(x, self.cls_token, self.pos_embed, ids, B, L)     # concat(cls, x) + pos_embed
-        if keep is None:
-            for blk in self.blocks:
-                x = blk(x, B, L + 1)
-        else:
-            for i, blk in enumerate(self.blocks):
-                x = blk(x, B, L + 1, keep[2 * i:2 * i + 2])
-        return x, cls_rows, B, L
+        keep = self._drop_path_keep(x.shape[0], x.device, drop_path_keep)
+        x, cls_rows, B, L = self.embed_tokens(x, self.cls_token, self.pos_embed)     # concat(cls, x) + pos_embed
+        return self.run_blocks(x, B, L + 1, keep), cls_rows, B, L
 
     def forward_features(self, x, drop_path_keep=None):
         x, cls_rows, _B, _L = self._tokens(x, drop_path_keep)
-        return self.norm(nn.gather_rows(x, cls_rows))                     # norm(x)[:, 0]: LayerNorm is per token
+        return self.cls_features(x, cls_rows, self.norm)
 
     def forward(self, x, drop_path_keep=None):
         return self.forward_features(x, drop_path_keep)
@@ -479,4 +308,4 @@ class MAE_ViT(VisionTransformer):
         x, cls_rows, B, L = self._tokens(x, drop_path_keep)
         if self.global_pool:
             return self.fc_norm(_PatchMeanFn.apply(x, cls_rows, B, L))
-        return self.norm(nn.gather_rows(x, cls_rows))
+        return self.cls_features(x, cls_rows, self.norm)

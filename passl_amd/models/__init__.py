@@ -8,14 +8,13 @@ kernels, same EncoderArena storage — and adapt the call convention of the v2 l
 (``model(sub_batch) -> loss tensor | dict``, passl/engine/loops/contrastive_learning_loop.py:52-54).
 """
 import copy
-import os
 import sys
 
 import torch
 
 from ..hip import nn as hnn
 from ..modeling.architectures import build_model as _build_v110
-from ..utils.checkpoint import load_lenient, load_pickle, to_numpy
+from ..utils.checkpoint import load_lenient, read_pdparams, save_pdparams
 
 __all__ = ['build_model', 'Model']
 
@@ -47,21 +46,13 @@ class ArchModel(Model):
 
     def load_pretrained(self, path, rank=0, finetune=False):
         """``path`` without extension, as in the reference (``<path>.pdparams``)."""
-        fn = path if os.path.exists(path) else path + '.pdparams'
-        if not os.path.exists(fn):
-            raise ValueError('Model pretrain path {} does not exists.'.format(fn))
-        sd = load_pickle(fn)
+        sd = read_pdparams(path, bare_ok=True)
         if 'state_dict' in sd:
             sd = sd['state_dict']
         load_lenient(self.arch, sd, what='pretrained model')
 
     def save(self, path, local_rank=0, rank=0):
-        import pickle
-        if rank != 0:
-            return
-        os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
-        with open(path + '.pdparams', 'wb') as f:
-            pickle.dump(to_numpy(dict(self.state_dict())), f, protocol=2)
+        save_pdparams(self, path, rank)
 
 
 # ---- factories (names follow the reference's `<method>_<backbone>` convention)

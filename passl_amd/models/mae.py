@@ -10,8 +10,6 @@ v2: the initialisation of the two tokens (both ``normal_(std=.02)``, :139-141; t
 token's and leaves the mask token at zero) and the ``Model`` contract (``load_pretrained`` / ``save``).  The flat
 parameter arena is built by the constructor, so the object trains as it is: ``tasks/ssl/mae/engine_pretrain.py``'s loop
 is mirrored in passl_amd/engine/loops/mae_pretrain_loop.py."""
-import os
-import pickle
 from functools import partial
 
 import torch
@@ -19,7 +17,7 @@ import torch
 from ..hip import nn as hnn
 from ..hip.nn import EncoderArena
 from ..modeling.backbones.mae import MAE as _HipMAE
-from ..utils.checkpoint import load_lenient, load_pickle, to_numpy
+from ..utils.checkpoint import load_pdparams, save_pdparams
 from .base_model import Model
 from .vision_transformer import VisionTransformer
 
@@ -59,18 +57,10 @@ class MaskedAutoencoderViT(_HipMAE, Model):
         return super().forward(imgs, mask_ratio, noise=noise)
 
     def load_pretrained(self, path, rank=0, finetune=False):
-        fn = path if os.path.exists(path) else path + '.pdparams'
-        if not os.path.exists(fn):
-            raise ValueError('Model pretrain path {} does not exists.'.format(fn))
-        load_lenient(self, load_pickle(fn), what='pretrained MAE')
-        self.sync_runtime_state()
+        load_pdparams(self, path, what='pretrained MAE', bare_ok=True)
 
     def save(self, path, local_rank=0, rank=0):
-        if rank != 0:
-            return
-        os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
-        with open(path + '.pdparams', 'wb') as f:
-            pickle.dump(to_numpy(dict(self.state_dict())), f, protocol=2)
+        save_pdparams(self, path, rank)
 
 
 class MAEVisionTransformer(VisionTransformer):

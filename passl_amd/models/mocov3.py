@@ -22,8 +22,6 @@ Execution (same building blocks as the MAE / CLIP paths, no new kernels):
   * keys of every rank: all_gather of the normalised keys (no gradient), labels ``arange(N) + N*rank``.
 """
 import math
-import os
-import pickle
 from functools import partial
 
 import torch
@@ -35,9 +33,9 @@ from ..core.sync_utils import collectives_active
 from ..hip import config, ops
 from ..hip import nn as hnn
 from ..hip.nn import EncoderArena
-from ..modeling.backbones.mae import Block, PatchEmbed, _GatherFn
 from ..modeling.heads.clip_head import _RowCEFn
-from ..utils.checkpoint import load_lenient, load_pickle, to_numpy
+from ..modules.vit import Block, PatchEmbed, ViTTrunk, uniform_
+from ..utils.checkpoint import dump_pdparams, load_lenient, load_pdparams, read_pdparams, save_pdparams
 from ..utils.infohub import runtime_info_hub
 from .base_model import Model
 from .utils.averaged_model import CosineEMA
@@ -57,11 +55,6 @@ def build_2d_sincos_position_embedding(embed_dim, h, w, temperature=10000.):
     out_h = grid_h.flatten()[:, None] * omega[None]
     pos = torch.cat([torch.sin(out_w), torch.cos(out_w), torch.sin(out_h), torch.cos(out_h)], dim=1)[None]
     return torch.cat([torch.zeros(1, 1, embed_dim), pos], dim=1)
-
-
-@torch.no_grad()
-def _uniform(w, a):
-    w.copy_((torch.rand(w.shape) * 2 - 1) * a)
 
 
 class _MLP(tnn.Sequential):
@@ -85,7 +78,7 @@ def build_mlp(num_layers, input_dim, mlp_dim, output_dim, last_bn=True):
         dim1 = input_dim if l == 0 else mlp_dim
         dim2 = output_dim if l == num_layers - 1 else mlp_dim
         lin = hnn.Linear(dim1, dim2, bias_attr=False)
-        _uniform(lin.weight, math.sqrt(6.0 / (dim1 + dim2)))
+        uniform_(lin.weight, math.sqrt(6.0 / (dim1 + dim2)))
         mlp.append(lin)
         if l < num_layers - 1:
             mlp.append(hnn.BatchNorm1D(dim2))
@@ -97,7 +90,7 @@ def build_mlp(num_layers, input_dim, mlp_dim, output_dim, last_bn=True):
     return _MLP(*mlp)
 
 
-class MoCoV3ViT(hnn.Layer):
+class MoCoV3ViT(ViTTrunk):
     def __init__(self, img_size=224, patch_size=16, in_chans=3, class_num=1000, embed_dim=768, depth=12,
                  num_heads=12, mlp_ratio=4, qkv_bias=False, qk_scale=None, drop_rate=0., attn_drop_rate=0.,
                  drop_path_rate=0., norm_layer='nn.LayerNorm', epsilon=1e-5, representation_size=None,
@@ -125,40 +118,26 @@ class MoCoV3ViT(hnn.Layer):
                                       for _ in range(depth)])
         self.norm = norm_layer(embed_dim)
         self.head = hnn.Linear(embed_dim, class_num) if class_num > 0 else None
-        self._ids = {}
         with torch.no_grad():
             for name, m in self.named_modules():
                 if isinstance(m, hnn.Linear):
                     if 'qkv' in name:      # treat the weights of Q, K, V separately
-                        _uniform(m.weight, math.sqrt(6. / float(m.weight.shape[1] // 3 + m.weight.shape[0])))
+                        uniform_(m.weight, math.sqrt(6. / float(m.weight.shape[1] // 3 + m.weight.shape[0])))
                     else:
-                        _uniform(m.weight, math.sqrt(6. / float(m.weight.shape[0] + m.weight.shape[1])))
+                        uniform_(m.weight, math.sqrt(6. / float(m.weight.shape[0] + m.weight.shape[1])))
                     if m.bias is not None:
                         m.bias.zero_()
             self.cls_token.copy_(torch.randn(self.cls_token.shape) * 1e-6)
             w = self.patch_embed.proj.weight
-            _uniform(w, math.sqrt(6. / float(3 * patch_size * patch_size + embed_dim)))
+            uniform_(w, math.sqrt(6. / float(3 * patch_size * patch_size + embed_dim)))
             self.patch_embed.proj.bias.zero_()
         if stop_grad_conv1:
             self.patch_embed.proj.weight.requires_grad_(False)
             self.patch_embed.proj.bias.requires_grad_(False)
 
-    def _identity_ids(self, B, L, device):
-        key = (B, L)
-        if key not in self._ids:
-            self._ids[key] = (torch.arange(L, dtype=torch.int32, device=device).repeat(B, 1).contiguous(),
-                              (torch.arange(B, dtype=torch.int32, device=device) * (L + 1)).contiguous())
-        return self._ids[key]
-
     def forward_features(self, x):
-        B = x.shape[0]
-        L = self.patch_embed.num_patches
-        x = self.patch_embed(x)                                           # [B*L, D]
-        ids, cls_rows = self._identity_ids(B, L, x.device)
-        x = _GatherFn.apply(x, self.cls_token, self.pos_embed, ids, ids, B, L)     # [cls | patches] + pos_embed
-        for blk in self.blocks:
-            x = blk(x, B, L + 1)
-        return self.norm(hnn.gather_rows(x, cls_rows))                    # norm(x)[:, 0]  (LayerNorm is per token)
+        x, cls_rows, B, L = self.embed_tokens(x, self.cls_token, self.pos_embed)     # [cls | patches] + pos_embed
+        return self.cls_features(self.run_blocks(x, B, L + 1), cls_rows, self.norm)
 
     def forward(self, x):
         x = self.forward_features(x)
@@ -200,20 +179,15 @@ class MoCoV3LinearProbe(MoCoV3ViT, Model):
         return r
 
     def load_pretrained(self, path, rank=0, finetune=False):
-        if not os.path.exists(path + '.pdparams'):
-            raise ValueError('Model pretrain path {} does not exists.'.format(path))
+        sd = read_pdparams(path)
         if finetune:
             raise NotImplementedError('finetune=True (head removal + position-embedding interpolation) belongs to the '
                                       'fine-tuning recipe')
-        load_lenient(self, load_pickle(path + '.pdparams'), what='pretrained model')
+        load_lenient(self, sd, what='pretrained model')
         self.sync_runtime_state()
 
     def save(self, path, local_rank=0, rank=0):
-        if rank != 0:
-            return
-        os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
-        with open(path + '.pdparams', 'wb') as f:
-            pickle.dump(to_numpy(dict(self.state_dict())), f, protocol=2)
+        save_pdparams(self, path, rank)
 
     def forward(self, x):
         self.arena_q.refresh()
@@ -325,24 +299,16 @@ class MoCoV3Pretrain(Model):
         return self.contrastive_loss(q1, k2) + self.contrastive_loss(q2, k1)
 
     def load_pretrained(self, path, rank=0, finetune=False):
-        if not os.path.exists(path + '.pdparams'):
-            raise ValueError('Model pretrain path {} does not exists.'.format(path))
-        load_lenient(self, load_pickle(path + '.pdparams'), what='pretrained model')
-        self.sync_runtime_state()
+        load_pdparams(self, path)
 
     def save(self, path, local_rank=0, rank=0):
         """<path>.pdparams = the whole state; <path>_base_encoder.pdparams = the backbone without the projector,
         prefix removed (mocov3.py:247-262)."""
-        if rank != 0:
-            return
-        os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
-        sd = to_numpy(dict(self.state_dict()))
-        with open(path + '.pdparams', 'wb') as f:
-            pickle.dump(sd, f, protocol=2)
-        enc = {k[len('base_encoder.'):]: v for k, v in sd.items()
-               if k.startswith('base_encoder') and not k.startswith('base_encoder.head')}
-        with open(path + '_base_encoder.pdparams', 'wb') as f:
-            pickle.dump(enc, f, protocol=2)
+        sd = save_pdparams(self, path, rank)
+        if sd is not None:
+            dump_pdparams({k[len('base_encoder.'):]: v for k, v in sd.items()
+                           if k.startswith('base_encoder') and not k.startswith('base_encoder.head')},
+                          path + '_base_encoder')
 
 
 def mocov3_vit_base(**kwargs):

@@ -8,14 +8,12 @@ The trunk IS the hot path's trunk (passl_amd/modeling/backbones/resnet.py: NHWC 
 BatchNorm statistics, streaming BatchNorm kernels, fused max-pool); this class adds the average pool -> flatten -> fc
 tail (fc = the GEMM kernel with a bias epilogue and fp32 output).  Bottleneck blocks, width 64, groups 1 only."""
 import math
-import os
-import pickle
 
 import torch
 
 from ..hip import nn as hnn
 from ..modeling.backbones.resnet import BottleneckBlock, ResNet as _Trunk
-from ..utils.checkpoint import load_lenient, load_pickle, to_numpy
+from ..utils.checkpoint import load_pdparams, save_pdparams
 from .base_model import Model
 
 __all__ = ['ResNet', 'BottleneckBlock', 'resnet50']
@@ -54,16 +52,10 @@ class ResNet(_Trunk, Model):
         return y
 
     def load_pretrained(self, path, rank=0, finetune=False):
-        if not os.path.exists(path + '.pdparams'):
-            raise ValueError('Model pretrain path {} does not exists.'.format(path))
-        load_lenient(self, load_pickle(path + '.pdparams'), what='pretrained model')
+        load_pdparams(self, path)
 
     def save(self, path, local_rank=0, rank=0):
-        if rank != 0:
-            return
-        os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
-        with open(path + '.pdparams', 'wb') as f:
-            pickle.dump(to_numpy(dict(self.state_dict())), f, protocol=2)
+        save_pdparams(self, path, rank)
 
 
 def resnet50(**kwargs):

@@ -15,8 +15,6 @@ BatchNorm layers then fold their slabs to fp64 moments, all-gather them (3 C dou
 them in rank order (csrc/bn.hip: bn_moments / bn_finalize_moments, bn_bwd_sums / bn_bwd_finalize_sums) — a two-rank run
 equals the one-rank run on the concatenated batch (tests/test_dp_gpu.py).
 """
-import os
-import pickle
 from functools import partial
 
 import torch
@@ -27,7 +25,7 @@ from ..hip import config
 from ..hip import nn as hnn
 from ..hip.nn import EncoderArena
 from ..loss.simsiam import neg_cosine_similarity
-from ..utils.checkpoint import load_lenient, load_pickle, to_numpy
+from ..utils.checkpoint import dump_pdparams, load_pdparams, save_pdparams
 from .base_model import Model
 from ..modeling.backbones.resnet import ResNet as _Trunk
 from .resnet import BottleneckBlock, ResNet, paddle_default_linear_init_
@@ -107,23 +105,15 @@ class SimSiamPretain(Model):
         return (neg_cosine_similarity(p1, z2) + neg_cosine_similarity(p2, z1)) * 0.5
 
     def load_pretrained(self, path, rank=0, finetune=False):
-        if not os.path.exists(path + '.pdparams'):
-            raise ValueError('Model pretrain path {} does not exists.'.format(path))
-        load_lenient(self, load_pickle(path + '.pdparams'), what='pretrained model')
-        self.sync_runtime_state()
+        load_pdparams(self, path)
 
     def save(self, path, local_rank=0, rank=0):
         """<path>.pdparams = the whole state; <path>_encoder.pdparams = the trunk without the projector, prefix
         removed (simsiam.py:113-126)."""
-        if rank != 0:
-            return
-        os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
-        sd = to_numpy(dict(self.state_dict()))
-        with open(path + '.pdparams', 'wb') as f:
-            pickle.dump(sd, f, protocol=2)
-        enc = {k[len('encoder.'):]: v for k, v in sd.items() if k.startswith('encoder') and not k.startswith('encoder.fc')}
-        with open(path + '_encoder.pdparams', 'wb') as f:
-            pickle.dump(enc, f, protocol=2)
+        sd = save_pdparams(self, path, rank)
+        if sd is not None:
+            dump_pdparams({k[len('encoder.'):]: v for k, v in sd.items()
+                           if k.startswith('encoder') and not k.startswith('encoder.fc')}, path + '_encoder')
 
 
 class SimSiamLinearProbe(ResNet):
@@ -161,10 +151,6 @@ class SimSiamLinearProbe(ResNet):
         r = super().load_state_dict(state_dict, strict=strict)
         self.sync_runtime_state()
         return r
-
-    def load_pretrained(self, path, rank=0, finetune=False):
-        super().load_pretrained(path, rank=rank, finetune=finetune)
-        self.sync_runtime_state()
 
     def forward(self, x):
         self.arena_q.refresh()                  # compute-dtype classifier operands from the fp32 masters

@@ -5,6 +5,7 @@ File format = a pickled dict of numpy arrays, the layout of the reference's ``sa
 (which adds the bookkeeping key ``StructuredToParameterName@@``  [Paddle-semantics]).  Because
 ``state_dict()`` here uses the reference's key names and logical shapes, a published ``.pdparams``
 loads without any transposition."""
+import os
 import pickle
 
 import numpy as np
@@ -61,4 +62,40 @@ def load_lenient(module, state_dict, logger=None, what='weights'):
         logger.warning('%s: %s is not found in the provided dict.' % (what, k))
     for k in res.unexpected_keys:
         logger.warning('%s: skip loading for %s (not in the model).' % (what, k))
+    return res
+
+
+def dump_pdparams(state, path):
+    """``state``: name -> numpy array, written as ``<path>.pdparams`` (pickle protocol 2, as paddle.save does)."""
+    os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
+    with open(path + '.pdparams', 'wb') as f:
+        pickle.dump(state, f, protocol=2)
+
+
+def save_pdparams(model, path, rank=0):
+    """``Model.save``: rank 0 writes ``model.state_dict()`` to ``<path>.pdparams``.  -> the written dict (None on the
+    other ranks), for the models that write a second file from it."""
+    if rank != 0:
+        return None
+    state = to_numpy(dict(model.state_dict()))
+    dump_pdparams(state, path)
+    return state
+
+
+def read_pdparams(path, bare_ok=False):
+    """``Model.load_pretrained``'s file: ``<path>.pdparams`` as in the reference; with ``bare_ok`` a ``path`` that
+    exists is taken as it is (a v110 checkpoint or an extracted-weights file given with its extension)."""
+    fn = path if bare_ok and os.path.exists(path) else path + '.pdparams'
+    if not os.path.exists(fn):
+        raise ValueError('Model pretrain path {} does not exists.'.format(fn if bare_ok else path))
+    return load_pickle(fn)
+
+
+def load_pdparams(model, path, what='pretrained model', bare_ok=False):
+    """read_pdparams + load_lenient, then ``model.sync_runtime_state()`` where the model has one (flat arenas that mirror
+    the parameters)."""
+    res = load_lenient(model, read_pdparams(path, bare_ok), what=what)
+    sync = getattr(model, 'sync_runtime_state', None)
+    if sync is not None:
+        sync()
     return res
