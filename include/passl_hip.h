@@ -590,6 +590,20 @@ int passl_hip_adamw(float* p, const float* g, float* m, float* v, int64_t n, flo
  * passl_hip_momentum_sgd_dev).  Both forms derive sqrt(1-b2^t) etc. inside the kernel: identical bits. */
 int passl_hip_adamw_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, float beta1,
                         float beta2, float epsilon, float weight_decay, float grad_scale, passl_stream_t stream);
+/* ... with parameter groups: a learning-rate multiplier and a weight decay per SEGMENT of the buffer, still one launch.
+ * seg_end / seg_lr_scale / seg_wd: device arrays of n_seg entries; seg_end holds ascending exclusive end offsets in
+ * elements, every one a multiple of 4 and the last one n (n % 4 == 0): element i belongs to the first segment with
+ * i < seg_end[s], slot padding to the parameter in front of it.  Per segment lr_s = hyper[0] * seg_lr_scale[s] (one
+ * fp32 multiply), then exactly the update of passl_hip_adamw with (lr_s, seg_wd[s]) — the two kernels share one
+ * device function, so a segment gets the bits passl_hip_adamw gives that slice alone.  The table is read from global
+ * memory (a binary search per workgroup tile): there is NO segment limit beyond n_seg fitting an int; the caller
+ * validates the table's contents (the library cannot read device memory on the host), the kernel keeps every access
+ * in bounds whatever it holds.  NULL pointers, n < 0, n % 4, n_seg <= 0, misalignment -> PASSL_EINVAL; n == 0 -> OK.
+ * Replaces the per-group optimizer loop of tasks/ssl/mae/main_finetune.py:478-484 (param_groups_lrd -> AdamW) and the
+ * lr_scale read of passl/optimizer/optimizer.py:117-123. */
+int passl_hip_adamw_groups_dev(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* seg_end,
+                               const float* seg_lr_scale, const float* seg_wd, int n_seg, const float* hyper,
+                               float beta1, float beta2, float epsilon, float grad_scale, passl_stream_t stream);
 
 /* ---------------------------------------------------------------- stochastic depth
  * Reference: class DropPath / drop_path(), passl_v110/modeling/backbones/mae.py:32-50; the ladder

@@ -516,6 +516,25 @@ __global__ void __launch_bounds__(kThreads) ordered_sum_kernel(const float* __re
 // ------------------------------------------------------------------ AdamW (flat buffer)
 // p *= 1 - lr*wd; m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2;
 // p -= lr_t * m / (sqrt(v) + eps_t),  lr_t = lr*sqrt(1-b2^t)/(1-b1^t), eps_t = eps*sqrt(1-b2^t)
+// The derived scalars and the element update, stated ONCE: the flat and the grouped kernel both call this, so a
+// segment updated with (lr*scale, wd_s) gets the bits the flat kernel gives a buffer of its own with those two values
+// (correctly rounded sqrt / divide: also the bits the host would compute).
+__device__ __forceinline__ void adamw_update(float* __restrict__ pp, const float* __restrict__ gp,
+                                             float* __restrict__ mp, float* __restrict__ vp, int count, float lr,
+                                             float wd, float b1p, float b2p, float eps, float b1, float b2, float gs) {
+  const float c2 = sqrtf(1.f - b2p);
+  const float decay = 1.f - lr * wd;
+  const float lr_t = lr * c2 / (1.f - b1p);
+  const float eps_t = eps * c2;
+#pragma unroll
+  for (int e = 0; e < count; ++e) {
+    const float gg = gp[e] * gs;
+    mp[e] = b1 * mp[e] + (1.f - b1) * gg;
+    vp[e] = b2 * vp[e] + (1.f - b2) * gg * gg;
+    pp[e] = pp[e] * decay - lr_t * (mp[e] / (sqrtf(vp[e]) + eps_t));
+  }
+}
+
 __global__ void __launch_bounds__(kThreads) adamw_kernel(float* __restrict__ p,
                                                          const float* __restrict__ g,
                                                          float* __restrict__ m, float* __restrict__ v,
@@ -523,12 +542,8 @@ __global__ void __launch_bounds__(kThreads) adamw_kernel(float* __restrict__ p,
                                                          const float* __restrict__ hyper, float wd, float eps,
                                                          float b1, float b2, float gs) {
   // the step-dependent scalars come by value or from device memory (hyper = {lr, beta1^t, beta2^t}: HIP-graph
-  // replays); the derived ones are computed here either way (correctly rounded sqrt / divide: same bits as on the host)
+  // replays); the derived ones are computed here either way
   if (hyper) { lr = hyper[0]; b1p = hyper[1]; b2p = hyper[2]; }
-  const float c2 = sqrtf(1.f - b2p);
-  const float decay = 1.f - lr * wd;
-  const float lr_t = lr * c2 / (1.f - b1p);
-  const float eps_t = eps * c2;
   const int64_t nv = n >> 2;
   const int64_t stride = (int64_t)gridDim.x * kThreads;
   for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < nv; i += stride) {
@@ -536,24 +551,53 @@ __global__ void __launch_bounds__(kThreads) adamw_kernel(float* __restrict__ p,
     const float4 gv = reinterpret_cast<const float4*>(g)[i];
     float4 mv = reinterpret_cast<float4*>(m)[i];
     float4 vv = reinterpret_cast<float4*>(v)[i];
-    float* pp = &pv.x; const float* gp = &gv.x; float* mp = &mv.x; float* vp = &vv.x;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float gg = gp[e] * gs;
-      mp[e] = b1 * mp[e] + (1.f - b1) * gg;
-      vp[e] = b2 * vp[e] + (1.f - b2) * gg * gg;
-      pp[e] = pp[e] * decay - lr_t * (mp[e] / (sqrtf(vp[e]) + eps_t));
-    }
+    adamw_update(&pv.x, &gv.x, &mv.x, &vv.x, 4, lr, wd, b1p, b2p, eps, b1, b2, gs);
     reinterpret_cast<float4*>(p)[i] = pv;
     reinterpret_cast<float4*>(m)[i] = mv;
     reinterpret_cast<float4*>(v)[i] = vv;
   }
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
     const int64_t i = (nv << 2) + threadIdx.x;
-    const float gg = g[i] * gs;
-    m[i] = b1 * m[i] + (1.f - b1) * gg;
-    v[i] = b2 * v[i] + (1.f - b2) * gg * gg;
-    p[i] = p[i] * decay - lr_t * (m[i] / (sqrtf(v[i]) + eps_t));
+    adamw_update(p + i, g + i, m + i, v + i, 1, lr, wd, b1p, b2p, eps, b1, b2, gs);
+  }
+}
+
+// ... with a learning-rate multiplier and a weight decay per SEGMENT of the buffer (parameter groups).  seg_end:
+// ascending exclusive end offsets, multiples of 4, the last one n — a float4 lies in one segment.  Same grid-stride
+// walk as the flat kernel.  The tile of one workgroup iteration (kThreads float4) starts at a wave-uniform offset: its
+// segment is found by a binary search through uniform (scalar-cache) loads of the table, resumed from the segment of
+// the block's previous tile (offsets ascend); a lane then steps forward while its own float4 lies beyond that segment
+// — no step at all unless a boundary falls inside the tile.  The table stays in global memory: no segment limit.
+// The cursor never leaves [0, n_seg) and the data accesses are bounded by n whatever the table holds.
+__global__ void __launch_bounds__(kThreads) adamw_groups_kernel(
+    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
+    const int64_t* __restrict__ seg_end, const float* __restrict__ seg_lr_scale, const float* __restrict__ seg_wd,
+    int n_seg, const float* __restrict__ hyper, float eps, float b1, float b2, float gs) {
+  const float lr = hyper[0], b1p = hyper[1], b2p = hyper[2];
+  const int64_t nv = n >> 2;
+  const int64_t stride = (int64_t)gridDim.x * kThreads;
+  int s0 = 0;
+  for (int64_t tile = (int64_t)blockIdx.x * kThreads; tile < nv; tile += stride) {
+    const int64_t first = tile << 2;                    // first element of the tile: uniform
+    int hi = n_seg - 1;
+    while (s0 < hi) {                                   // first segment with first < seg_end[s]
+      const int mid = (s0 + hi) >> 1;
+      if (first < seg_end[mid]) hi = mid; else s0 = mid + 1;
+    }
+    const int64_t i = tile + threadIdx.x;
+    if (i >= nv) continue;
+    int s = s0;
+    while (s + 1 < n_seg && (i << 2) >= seg_end[s]) ++s;
+    const float lr_s = lr * seg_lr_scale[s];
+    const float wd_s = seg_wd[s];
+    float4 pv = reinterpret_cast<float4*>(p)[i];
+    const float4 gv = reinterpret_cast<const float4*>(g)[i];
+    float4 mv = reinterpret_cast<float4*>(m)[i];
+    float4 vv = reinterpret_cast<float4*>(v)[i];
+    adamw_update(&pv.x, &gv.x, &mv.x, &vv.x, 4, lr_s, wd_s, b1p, b2p, eps, b1, b2, gs);
+    reinterpret_cast<float4*>(p)[i] = pv;
+    reinterpret_cast<float4*>(m)[i] = mv;
+    reinterpret_cast<float4*>(v)[i] = vv;
   }
 }
 
@@ -832,4 +876,22 @@ extern "C" int passl_hip_adamw_dev(float* p, const float* g, float* m, float* v,
                                    passl_stream_t stream) {
   if (!hyper) return PASSL_EINVAL;
   return adamw_impl(p, g, m, v, n, 0.f, 0.f, 0.f, hyper, beta1, beta2, epsilon, weight_decay, grad_scale, stream);
+}
+
+extern "C" int passl_hip_adamw_groups_dev(float* p, const float* g, float* m, float* v, int64_t n,
+                                          const int64_t* seg_end, const float* seg_lr_scale, const float* seg_wd,
+                                          int n_seg, const float* hyper, float beta1, float beta2, float epsilon,
+                                          float grad_scale, passl_stream_t stream) {
+  if (!p || !g || !m || !v || !hyper || !seg_end || !seg_lr_scale || !seg_wd || n < 0 || (n & 3) || n_seg <= 0 ||
+      !aligned16(p) || !aligned16(g) || !aligned16(m) || !aligned16(v) ||
+      (reinterpret_cast<uintptr_t>(seg_end) & 7u) || (reinterpret_cast<uintptr_t>(seg_lr_scale) & 3u) ||
+      (reinterpret_cast<uintptr_t>(seg_wd) & 3u) || (reinterpret_cast<uintptr_t>(hyper) & 3u))
+    return PASSL_EINVAL;
+  if (n == 0) return PASSL_OK;
+  int64_t b = ((n >> 2) + kThreads - 1) / kThreads;       // the flat kernel's grid
+  if (b > 2048) b = 2048;
+  hipLaunchKernelGGL(adamw_groups_kernel, dim3((unsigned)b), dim3(kThreads), 0, as_stream(stream), p, g, m, v, n,
+                     seg_end, seg_lr_scale, seg_wd, n_seg, hyper, epsilon, beta1, beta2, grad_scale);
+  PASSL_RETURN_IF_LAUNCH_FAILED();
+  return PASSL_OK;
 }

@@ -137,6 +137,13 @@ class Trainer:
                 cfg.lr_scheduler, self.iters_per_epoch, epochs=cfg.get('epochs', None),
                 batch_size=int(cfg.dataloader.train.sampler.get('batch_size', 0) or 0) * self.world_size or None)
         self.optimizer = build_optimizer(cfg.optimizer, self.lr_scheduler, [self.model])
+        if getattr(self.optimizer, 'grouped', False):
+            # (the reference's param_groups_lrd prints its groups, tasks/ssl/mae/util/lr_decay.py:73)
+            table = self.optimizer.param_table()
+            scales = sorted({s for _n, s, _w in table})
+            self.logger.info('AdamW parameter groups: {} parameters, {} lr multipliers {:.4g} .. {:.4g}, {} parameters '
+                             'without weight decay'.format(len(table), len(scales), scales[0], scales[-1],
+                                                           sum(1 for _n, _s, w in table if w == 0.0)))
 
         self.use_amp = cfg.get('use_amp', False)
         self.scaler = None

@@ -4,6 +4,7 @@ torch is used for device memory and the current stream only.  Every function lau
 kernels from libpassl_hip.so; host tensors are refused (lib.ptr raises).
 """
 import ctypes as C
+import math
 
 import torch
 
@@ -910,6 +911,45 @@ def adamw_dev(p, g, m, v, hyper, b1, b2, eps, wd, grad_scale=1.0):
     """hyper: device float32 [lr, beta1^t, beta2^t], read when the kernel runs."""
     L.check(_lib().passl_hip_adamw_dev(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), p.numel(), L.ptr(hyper), b1, b2, eps,
                                        wd, grad_scale, L.stream()), 'adamw_dev')
+
+
+def adamw_groups_table(seg_end, seg_lr_scale, seg_wd, n, device):
+    """The segment table of passl_hip_adamw_groups_dev, validated HERE, once, on the host (the kernel trusts it):
+    seg_end ascending exclusive end offsets in elements, every one a positive multiple of 4, the last one ``n``;
+    finite multipliers; weight decays >= 0.  -> dict of device arrays (int64 / float32 / float32) + n, n_seg."""
+    seg_end = [int(e) for e in seg_end]
+    scales = [float(x) for x in seg_lr_scale]
+    wds = [float(x) for x in seg_wd]
+    if not seg_end or not len(seg_end) == len(scales) == len(wds):
+        raise ValueError('adamw_groups_table: %d ends, %d multipliers, %d weight decays (equal and >= 1 wanted)'
+                         % (len(seg_end), len(scales), len(wds)))
+    n = int(n)
+    if n % 4:
+        raise ValueError('adamw_groups_table: n = %d is not a multiple of 4' % n)
+    prev = 0
+    for i, e in enumerate(seg_end):
+        if e % 4:
+            raise ValueError('adamw_groups_table: seg_end[%d] = %d is not a multiple of 4' % (i, e))
+        if e <= prev:
+            raise ValueError('adamw_groups_table: seg_end[%d] = %d does not ascend (previous end %d)' % (i, e, prev))
+        prev = e
+    if prev != n:
+        raise ValueError('adamw_groups_table: the last segment ends at %d, the buffer holds %d elements' % (prev, n))
+    for i, (sc, wd) in enumerate(zip(scales, wds)):
+        if not math.isfinite(sc) or not math.isfinite(wd) or wd < 0:
+            raise ValueError('adamw_groups_table: segment %d has multiplier %r, weight decay %r' % (i, sc, wd))
+    return dict(seg_end=torch.tensor(seg_end, dtype=torch.int64, device=device),
+                seg_lr_scale=torch.tensor(scales, dtype=torch.float32, device=device),
+                seg_wd=torch.tensor(wds, dtype=torch.float32, device=device), n=n, n_seg=len(seg_end))
+
+
+def adamw_groups_dev(p, g, m, v, table, hyper, b1, b2, eps, grad_scale=1.0):
+    """AdamW with a learning-rate multiplier and a weight decay per segment (``table``: adamw_groups_table)."""
+    if table['n'] != p.numel():
+        raise ValueError('adamw_groups_dev: the table covers %d elements, the buffer holds %d' % (table['n'], p.numel()))
+    L.check(_lib().passl_hip_adamw_groups_dev(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), p.numel(), L.ptr(table['seg_end']),
+                                              L.ptr(table['seg_lr_scale']), L.ptr(table['seg_wd']), table['n_seg'],
+                                              L.ptr(hyper), b1, b2, eps, grad_scale, L.stream()), 'adamw_groups_dev')
 
 
 # ------------------------------------------------------------------ CLIP

@@ -241,6 +241,11 @@ class VisionTransformer(ViTTrunk):
                     if m.bias is not None:
                         m.bias.zero_()
 
+    def get_num_layers(self):
+        """What build_optimizer's layer-wise lr decay asks the backbone (passl_v110/solver/builder.py:182), as the
+        reference's beit_ft.py:493 answers it; the reference's own MAE_ViT has no such method."""
+        return len(self.blocks)
+
     # -- stochastic depth ------------------------------------------------------------------------------------------
     def set_drop_path_seed(self, seed, step=0):
         """Key of the Philox draw and the value of the step counter (tests; a resumed run restarts at step 0)."""

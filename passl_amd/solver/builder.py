@@ -58,15 +58,33 @@ def build_lr_scheduler_simclr(cfg, iters_per_epoch, batch_size, epochs, current_
 
 
 def build_optimizer(cfg, lr_scheduler, model_list=None):
+    """passl_v110/solver/builder.py:162-216.  ``layer_decay`` < 1: parameter groups by the v110 rule (solver/lr_decay.py)
+    over ``model_list[0]`` with ``num_layers = model_list[0].backbone.get_num_layers()``; ``exclude_from_weight_decay``:
+    the Paddle names of the parameters whose state-dict name contains one of the strings get no decay (:203-214)."""
     cfg = copy.deepcopy(cfg)
     name = cfg.pop('name')
-    if 'layer_decay' in cfg and float(cfg.pop('layer_decay')) < 1.0:
-        raise NotImplementedError('layer-wise lr decay (ViT fine-tuning) is outside the MoCo hot path')
+    layer_decay = float(cfg.pop('layer_decay')) if 'layer_decay' in cfg else 1.0
     if 'grad_clip' in cfg:
         raise NotImplementedError('grad_clip is not used by configs/moco and is not built')
-    parameters = sum([list(m.parameters()) for m in model_list], []) if model_list else None
+    if layer_decay < 1.0:
+        from .lr_decay import LayerDecayValueAssigner, get_parameter_groups
+        num_layers = model_list[0].backbone.get_num_layers()
+        assigner = LayerDecayValueAssigner(list(layer_decay ** (num_layers + 1 - i) for i in range(num_layers + 2)))
+        parameters = get_parameter_groups(cfg, model_list[0], get_num_layer=assigner.get_layer_id,
+                                          get_layer_scale=assigner.get_scale)
+    else:
+        parameters = sum([list(m.parameters()) for m in model_list], []) if model_list else None
     if 'Lars' in name or 'Lamb' in name:
         cfg['parameter_list'] = parameters
     else:
         cfg['parameters'] = parameters
+        if 'exclude_from_weight_decay' in cfg:
+            from .optimizer import paddle_param_names
+            ex_decay_cfg = cfg.pop('exclude_from_weight_decay')
+            excluded = set()
+            for model in model_list:
+                pnames = paddle_param_names(model)
+                excluded.update(pnames[id(p)] for n, p in model.named_parameters()
+                                if any(nd in n for nd in ex_decay_cfg))
+            cfg['apply_decay_param_fun'] = lambda pname: pname not in excluded
     return OPTIMIZERS.get(name)(lr_scheduler, **cfg)

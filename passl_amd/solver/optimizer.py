@@ -170,9 +170,12 @@ def _paddle_auto_names(arena):
     in construction order — what LarsMomentumOptimizer matches ``exclude_from_weight_decay``
     against (param.name, not the state_dict key)  [Paddle-semantics]."""
     from ..hip import nn as hnn
-    counters, names = {}, []
+    counters, names, seen = {}, [], set()
     for mod in arena.module.modules():
-        own = [n for n, p in mod._parameters.items() if p is not None]
+        # the arena's own slots only, each once (EncoderArena skips excluded sub-layers and shared parameters)
+        own = [n for n, p in mod._parameters.items()
+               if p is not None and getattr(p, '_passl_arena', None) is arena and id(p) not in seen]
+        seen.update(id(mod._parameters[n]) for n in own)
         if not own:
             continue
         if isinstance(mod, hnn.Conv2D):
@@ -187,9 +190,34 @@ def _paddle_auto_names(arena):
             kind = type(mod).__name__.lower()
         idx = counters.get(kind, 0)
         counters[kind] = idx + 1
+        # a layer's own parameters count up per kind, biases apart (unique_name.generate(<layer>.w / .b)): weight / bias
+        # are w_0 / b_0, a ViT's cls_token / pos_embed w_0 / w_1
+        nw = nb = 0
         for n in own:
-            names.append('%s_%d.%s' % (kind, idx, 'w_0' if n == 'weight' else 'b_0'))
+            if n == 'bias':
+                names.append('%s_%d.b_%d' % (kind, idx, nb))
+                nb += 1
+            else:
+                names.append('%s_%d.w_%d' % (kind, idx, nw))
+                nw += 1
     return names
+
+
+def paddle_param_names(model):
+    """{id(parameter): Paddle auto-name} of every arena parameter of ``model`` (what ``p.name`` is in the reference's
+    build_optimizer, passl_v110/solver/builder.py:209-213).  The names count per arena, like _paddle_auto_names."""
+    out, arenas = {}, []
+    params = list(model.parameters())
+    for p in params:
+        a = getattr(p, '_passl_arena', None)
+        if a is not None and a not in arenas:
+            arenas.append(a)
+    names = {id(a): _paddle_auto_names(a) for a in arenas}
+    for p in params:
+        a = getattr(p, '_passl_arena', None)
+        if a is not None:
+            out[id(p)] = names[id(a)][p._passl_index]
+    return out
 
 
 @OPTIMIZERS.register()
@@ -328,8 +356,21 @@ class AdamW(_DeviceHyper):
         p *= 1 - lr*wd;  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;
         p -= lr*sqrt(1-b2^t)/(1-b1^t) * m / (sqrt(v) + eps*sqrt(1-b2^t))
     A float ``weight_decay`` decays EVERY trainable parameter (configs/mae/mae_vit_b_pretrain.yaml has no
-    exclusion list; fixed sin-cos embeddings are buffers and are not touched)."""
+    exclusion list; fixed sin-cos embeddings are buffers and are not touched).
+
+    Parameter groups (ViT fine-tuning: solver/lr_decay.py, build_optimizer's ``layer_decay``): ``parameters`` may be a
+    list of dicts {params, weight_decay (default: the optimizer's), learning_rate | lr_scale}.  The multiplier is
+    spelled ``learning_rate`` in Paddle's groups (a group's learning_rate multiplies the optimizer's
+    [Paddle-semantics]) and ``lr_scale`` in the v2 tree (passl/optimizer/optimizer.py:117-123); ``lr_ratio(param)``
+    multiplies it; ``apply_decay_param_fun(name)`` — name = the Paddle auto-name (_paddle_auto_names) — switches the
+    decay of a parameter off.  Every trainable parameter of an arena is listed exactly once.  The result is ONE table
+    per arena (arena order, adjacent parameters with equal (multiplier, decay) merged; slot padding goes with the
+    parameter in front of it) for the grouped kernel (ops.adamw_groups_dev).  Multipliers all exactly 1.0 and decays
+    all equal = the flat kernel, launch for launch what a plain list gets.  The table is configuration, not state:
+    state_dict() holds the flat moments only."""
     type = 'adamw'
+
+    _GROUP_KEYS = ('params', 'weight_decay', 'learning_rate', 'lr_scale')
 
     def __init__(self, learning_rate=0.001, beta1=0.9, beta2=0.999, epsilon=1e-08, parameters=None,
                  weight_decay=0.01, lr_ratio=None, apply_decay_param_fun=None, grad_clip=None,
@@ -343,30 +384,97 @@ class AdamW(_DeviceHyper):
             beta1, beta2 = (float(b) for b in betas)
         if eps is not None:
             epsilon = eps
-        if apply_decay_param_fun is not None or lr_ratio is not None or grad_clip is not None:
-            raise NotImplementedError('per-parameter decay / lr ratios / clipping are not used by the MAE '
-                                      'pre-training config and are not built')
+        if grad_clip is not None:
+            raise NotImplementedError('gradient clipping is not built')
         self._learning_rate = learning_rate
         self._b1, self._b2, self._eps = float(beta1), float(beta2), float(epsilon)
         self._wd = float(weight_decay) if weight_decay else 0.0
-        params = [p for p in (parameters or []) if p.requires_grad]
+        if self._wd < 0:
+            raise ValueError('weight_decay must be >= 0, got %r' % (weight_decay,))
+        # one (parameter, multiplier, decay) per listed trainable parameter
+        listed = []
+        parameters = list(parameters or [])
+        if parameters and all(isinstance(g, dict) for g in parameters):
+            for gi, group in enumerate(parameters):
+                unknown = [k for k in group if k not in self._GROUP_KEYS]
+                if unknown or 'params' not in group:
+                    raise ValueError('parameter group %d: keys %r (known: %r, params required)'
+                                     % (gi, sorted(group), self._GROUP_KEYS))
+                if 'learning_rate' in group and 'lr_scale' in group:
+                    raise ValueError('parameter group %d gives its multiplier twice (learning_rate and lr_scale)' % gi)
+                scale = float(group.get('learning_rate', group.get('lr_scale', 1.0)))
+                wd = group.get('weight_decay', None)
+                wd = self._wd if wd is None else float(wd)
+                if wd < 0:
+                    raise ValueError('parameter group %d: weight_decay must be >= 0, got %r' % (gi, wd))
+                listed += [(p, scale, wd) for p in group['params'] if p.requires_grad]
+        elif any(isinstance(g, dict) for g in parameters):
+            raise ValueError('parameters: a list of tensors or a list of group dicts, not a mixture')
+        else:
+            listed = [(p, 1.0, self._wd) for p in parameters if p.requires_grad]
         arenas = []
-        for p in params:
+        seen = {}
+        for p, _s, _w in listed:
             a = getattr(p, '_passl_arena', None)
             if a is None:
                 raise NotImplementedError('AdamW optimises parameters that live in an EncoderArena')
+            if id(p) in seen:
+                raise ValueError('a parameter appears more than once in the parameter list / groups')
+            seen[id(p)] = True
             if a not in arenas:
                 arenas.append(a)
         for a in arenas:
-            if sum(1 for p in params if p._passl_arena is a) != len(a.param_slices):
+            if sum(1 for p, _s, _w in listed if p._passl_arena is a) != len(a.param_slices):
                 raise NotImplementedError('optimising a subset of an arena is not supported')
-        self._parameter_list = params
+        self._parameter_list = [p for p, _s, _w in listed]
         self._arenas = arenas
+        self._param_table = []         # per arena: [(paddle auto-name, multiplier, decay)] in arena order
+        self._tables = []              # per arena: None (flat kernel with _flat_wd) or the device table
+        self._flat_wd = []
+        for a in arenas:
+            names = _paddle_auto_names(a)
+            assert len(names) == len(a.param_slices)
+            rows = [None] * len(names)
+            for p, scale, wd in listed:
+                if p._passl_arena is not a:
+                    continue
+                name = names[p._passl_index]
+                if lr_ratio is not None:
+                    scale = scale * float(lr_ratio(p))
+                if apply_decay_param_fun is not None and not apply_decay_param_fun(name):
+                    wd = 0.0
+                rows[p._passl_index] = (name, scale, wd)
+            self._param_table.append(rows)
+            if all(s == 1.0 for _n, s, _w in rows) and len({w for _n, _s, w in rows}) == 1:
+                self._tables.append(None)
+                self._flat_wd.append(rows[0][2])
+                continue
+            ends = [off for off, _n in a.param_slices[1:]] + [a.n_train]
+            seg_end, seg_scale, seg_wd = [], [], []
+            for end, (_name, scale, wd) in zip(ends, rows):
+                if seg_end and (seg_scale[-1], seg_wd[-1]) == (scale, wd):
+                    seg_end[-1] = end
+                else:
+                    seg_end.append(end)
+                    seg_scale.append(scale)
+                    seg_wd.append(wd)
+            self._tables.append(ops.adamw_groups_table(seg_end, seg_scale, seg_wd, a.n_train, a.device))
+            self._flat_wd.append(None)
         self._m = [torch.zeros_like(a.flat[:a.n_train]) for a in arenas]
         self._v = [torch.zeros_like(a.flat[:a.n_train]) for a in arenas]
         self._t = 0
         self.grad_scale = 1.0
         self._init_hyper(arenas[0].device if arenas else torch.device('cpu'))
+
+    @property
+    def grouped(self):
+        """True when some arena takes the grouped launch (a multiplier != 1 or more than one decay)."""
+        return any(t is not None for t in self._tables)
+
+    def param_table(self):
+        """[(name, lr multiplier, weight decay)] of every parameter in arena order (arena after arena); name = the
+        Paddle auto-name ``apply_decay_param_fun`` was asked about."""
+        return [row for rows in self._param_table for row in rows]
 
     def _host_values(self):
         self._t += 1
@@ -385,10 +493,14 @@ class AdamW(_DeviceHyper):
     @torch.no_grad()
     def step(self):
         hyper = self._hyper_for_step()
-        for a, m, v in zip(self._arenas, self._m, self._v):
+        for a, m, v, table, wd in zip(self._arenas, self._m, self._v, self._tables, self._flat_wd):
             _grads_complete(a)
-            ops.adamw_dev(a.flat[:a.n_train], a.grads, m, v, hyper, self._b1, self._b2, self._eps, self._wd,
-                          self.grad_scale)
+            if table is None:
+                ops.adamw_dev(a.flat[:a.n_train], a.grads, m, v, hyper, self._b1, self._b2, self._eps, wd,
+                              self.grad_scale)
+            else:
+                ops.adamw_groups_dev(a.flat[:a.n_train], a.grads, m, v, table, hyper, self._b1, self._b2, self._eps,
+                                     self.grad_scale)
 
     def state_dict(self):
         sd = {'t': self._t}
