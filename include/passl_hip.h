@@ -605,6 +605,46 @@ int passl_hip_adamw_groups_dev(float* p, const float* g, float* m, float* v, int
                                const float* seg_lr_scale, const float* seg_wd, int n_seg, const float* hyper,
                                float beta1, float beta2, float epsilon, float grad_scale, passl_stream_t stream);
 
+/* ---------------------------------------------------------------- global-norm gradient clipping (AdamW)
+ * Reference: class ClipGradByGlobalNorm and clip_grad_norm_, passl/core/grad_clip.py:30-139, called once per parameter
+ * group by passl/optimizer/adamw.py:53-55.  For one SET of parameters
+ *     norm = sqrtf(sum (g*grad_scale)^2),   coef = 1                                    if !always_clip && norm <= clip_norm
+ *                                                = min(clip_norm / (norm + 1e-6f), clip_norm_max)   otherwise
+ * (a non-finite norm is "not <=": its coefficient propagates).  Three steps, none of which returns anything to the
+ * host and none of which uses an atomic — the result is bit-identical wherever the inputs are:
+ *   1. passl_hip_grad_sumsq, one launch per gradient buffer: partial[c] = sum over chunk c = g[chunk_off[c],
+ *      chunk_off[c] + chunk_len[c]) of fp32(g*grad_scale)^2, one workgroup per chunk, one fixed order.  A chunk holds at
+ *      most PASSL_GRAD_CLIP_CHUNK elements; offsets and lengths are multiples of 4.  The caller builds the table so that
+ *      no chunk crosses the boundary of a set or covers a parameter left out of clipping, and hands every launch its own
+ *      range of ONE partial buffer.  Workspace: n_chunks floats.
+ *   2. passl_hip_grad_clip_finalize, one launch: out[s] = {norm, coef} (2 floats per set) from the partials
+ *      set_chunks[set_ptr[s] .. set_ptr[s+1]) (a CSR index into the partial buffer: n_sets + 1 / n_idx int32), summed in
+ *      index order by one workgroup per set; sqrtf and the division are correctly rounded.  clip_norm_max: +inf for "no
+ *      upper limit".  clip_norm and clip_norm_max must be > 0.
+ *   3. the clip variants of the update: gg = (g*grad_scale)*coef, then exactly passl_hip_adamw_dev /
+ *      passl_hip_adamw_groups_dev (one shared device function).  The flat variant reads coef[0]; the grouped variant
+ *      reads clip[2*seg_set[s] + 1] from the {norm, coef} table of step 2, seg_set[s] outside [0, n_sets) (-1) meaning
+ *      coefficient 1.  n % 4 == 0 for both.
+ * The gradient buffer is NOT rewritten (the reference scales it in place).  The library cannot read device tables on the
+ * host: the caller validates their contents, the kernels keep every access inside [0, n) / the partial buffer whatever
+ * they hold.  NULL pointers, n <= 0 (sumsq), n < 0 (updates), n % 4, counts <= 0, misalignment -> PASSL_EINVAL.
+ * passl_hip_grad_clip_chunk(PASSL_HIP_ABI_VERSION) returns PASSL_GRAD_CLIP_CHUNK as the library was built (any other
+ * argument: PASSL_EINVAL). */
+#define PASSL_GRAD_CLIP_CHUNK 16384
+int passl_hip_grad_clip_chunk(int abi_version);
+int passl_hip_grad_sumsq(const float* g, int64_t n, const int64_t* chunk_off, const int32_t* chunk_len, int n_chunks,
+                         float grad_scale, float* partial, passl_stream_t stream);
+int passl_hip_grad_clip_finalize(const float* partial, int n_partial, const int32_t* set_ptr, const int32_t* set_chunks,
+                                 int n_idx, int n_sets, float clip_norm, float clip_norm_max, int always_clip, float* out,
+                                 passl_stream_t stream);
+int passl_hip_adamw_clip_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper,
+                             const float* coef, float beta1, float beta2, float epsilon, float weight_decay,
+                             float grad_scale, passl_stream_t stream);
+int passl_hip_adamw_groups_clip_dev(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* seg_end,
+                                    const float* seg_lr_scale, const float* seg_wd, const int32_t* seg_set, int n_seg,
+                                    const float* hyper, const float* clip, int n_sets, float beta1, float beta2,
+                                    float epsilon, float grad_scale, passl_stream_t stream);
+
 /* ---------------------------------------------------------------- stochastic depth
  * Reference: class DropPath / drop_path(), passl_v110/modeling/backbones/mae.py:32-50; the ladder
  * linspace(0, drop_path_rate, depth) :234; the two uses per Block :186-187.  Token rows [B*T][C] in `dtype`, sample b

@@ -536,3 +536,114 @@ extern "C" int passl_hip_larc_momentum_dev(float* p, const float* g, float* v, c
   PASSL_RETURN_IF_LAUNCH_FAILED();
   return PASSL_OK;
 }
+
+// ------------------------------------------------------------------ global-norm gradient clipping
+// passl/core/grad_clip.py ClipGradByGlobalNorm:  norm = sqrt(sum (g*gs)^2) over a SET of parameters;
+// coef = 1 if !always_clip and norm <= clip_norm, else min(clip_norm / (norm + 1e-6), clip_norm_max).  Two kernels, no
+// atomics (the coefficient must be BIT-IDENTICAL on every data-parallel rank): a chunk's sum in one fixed order, then a
+// set's chunks in one fixed order.  The coefficient stays on the device; the AdamW clip variants (vit.hip) read it.
+namespace {
+
+constexpr int kClipChunk = PASSL_GRAD_CLIP_CHUNK;       // elements per workgroup: the same on every device
+constexpr int kClipLoads = kClipChunk / (4 * kThreads);    // float4 loads per lane
+static_assert(kClipChunk % (16 * kThreads) == 0, "a lane's loads split over four accumulators");
+
+__device__ __forceinline__ float sq4(const float4 v, float gs) {
+  const float x = v.x * gs, y = v.y * gs, z = v.z * gs, w = v.w * gs;      // square fp32(g * gs), as the update uses it
+  return x * x + y * y + z * z + w * w;
+}
+
+// partial[block] = sum of (g*gs)^2 over chunk `block` = g[off, off + len).  Lane t takes the float4s t, t + 256, ... of
+// the chunk: 16-byte loads, all of them independent of the four accumulators, so a lane keeps kClipLoads loads in flight.
+// Whatever the table holds, the chunk is cut to [0, n): off to a multiple of 4 inside the buffer, len to what is left.
+__global__ void __launch_bounds__(kThreads) grad_sumsq_kernel(
+    const float* __restrict__ g, int64_t n, const int64_t* __restrict__ chunk_off,
+    const int32_t* __restrict__ chunk_len, float gs, float* __restrict__ partial) {
+  __shared__ float red[4];
+  int64_t off = chunk_off[blockIdx.x];
+  int64_t len = chunk_len[blockIdx.x];
+  if (off < 0 || off > n) { off = 0; len = 0; }
+  off &= ~(int64_t)3;
+  if (len > kClipChunk) len = kClipChunk;
+  if (len > n - off) len = n - off;
+  const int nv = len > 0 ? (int)(len >> 2) : 0;
+  const float4* __restrict__ gp = reinterpret_cast<const float4*>(g + off);
+  float4 v[kClipLoads];
+#pragma unroll
+  for (int j = 0; j < kClipLoads; ++j) {
+    const int i = j * kThreads + (int)threadIdx.x;
+    v[j] = i < nv ? gp[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+#pragma unroll
+  for (int j = 0; j < kClipLoads; j += 4) {
+    a0 += sq4(v[j], gs);
+    a1 += sq4(v[j + 1], gs);
+    a2 += sq4(v[j + 2], gs);
+    a3 += sq4(v[j + 3], gs);
+  }
+  const float s = block_sum((a0 + a1) + (a2 + a3), red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// out[set] = {norm, coef}.  One workgroup per set; the set's chunks come through a CSR index (sets are not contiguous
+// in arena order: decay / no-decay groups interleave, a global set spans arenas).  Lane t adds the entries t, t + 256,
+// ... in order.  sqrtf and the division are correctly rounded: the host computes the same bits from the same sum.
+__global__ void __launch_bounds__(kThreads) grad_clip_finalize_kernel(
+    const float* __restrict__ partial, int n_partial, const int32_t* __restrict__ set_ptr,
+    const int32_t* __restrict__ set_chunks, int n_idx, float clip_norm, float clip_norm_max, int always_clip,
+    float* __restrict__ out) {
+  __shared__ float red[4];
+  int lo = set_ptr[blockIdx.x], hi = set_ptr[blockIdx.x + 1];
+  if (lo < 0) lo = 0;
+  if (hi > n_idx) hi = n_idx;
+  float s = 0.f;
+  for (int i = lo + (int)threadIdx.x; i < hi; i += kThreads) {
+    const int c = set_chunks[i];
+    if (c >= 0 && c < n_partial) s += partial[c];
+  }
+  s = block_sum(s, red);
+  if (threadIdx.x == 0) {
+    const float norm = sqrtf(s);
+    float coef = 1.f;
+    if (always_clip || !(norm <= clip_norm)) {          // a NaN norm is "not <=": the NaN coefficient propagates
+      coef = clip_norm / (norm + 1e-6f);
+      if (coef > clip_norm_max) coef = clip_norm_max;
+    }
+    out[2 * blockIdx.x] = norm;
+    out[2 * blockIdx.x + 1] = coef;
+  }
+}
+
+}  // namespace
+
+extern "C" int passl_hip_grad_clip_chunk(int abi_version) {
+  return abi_version == PASSL_HIP_ABI_VERSION ? kClipChunk : PASSL_EINVAL;
+}
+
+extern "C" int passl_hip_grad_sumsq(const float* g, int64_t n, const int64_t* chunk_off, const int32_t* chunk_len,
+                                    int n_chunks, float grad_scale, float* partial, passl_stream_t stream) {
+  if (!g || !chunk_off || !chunk_len || !partial || n <= 0 || (n & 3) || n_chunks <= 0 || !aligned16(g) ||
+      (reinterpret_cast<uintptr_t>(chunk_off) & 7u) || (reinterpret_cast<uintptr_t>(chunk_len) & 3u) ||
+      (reinterpret_cast<uintptr_t>(partial) & 3u))
+    return PASSL_EINVAL;
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)n_chunks), dim3(kThreads), 0, as_stream(stream), g, n,
+                     chunk_off, chunk_len, grad_scale, partial);
+  PASSL_RETURN_IF_LAUNCH_FAILED();
+  return PASSL_OK;
+}
+
+extern "C" int passl_hip_grad_clip_finalize(const float* partial, int n_partial, const int32_t* set_ptr,
+                                            const int32_t* set_chunks, int n_idx, int n_sets, float clip_norm,
+                                            float clip_norm_max, int always_clip, float* out,
+                                            passl_stream_t stream) {
+  if (!partial || !set_ptr || !set_chunks || !out || n_partial <= 0 || n_idx <= 0 || n_sets <= 0 ||
+      !(clip_norm > 0.f) || !(clip_norm_max > 0.f) || clip_norm > 3.0e38f ||
+      (reinterpret_cast<uintptr_t>(partial) & 3u) || (reinterpret_cast<uintptr_t>(set_ptr) & 3u) ||
+      (reinterpret_cast<uintptr_t>(set_chunks) & 3u) || (reinterpret_cast<uintptr_t>(out) & 3u))
+    return PASSL_EINVAL;
+  hipLaunchKernelGGL(grad_clip_finalize_kernel, dim3((unsigned)n_sets), dim3(kThreads), 0, as_stream(stream), partial,
+                     n_partial, set_ptr, set_chunks, n_idx, clip_norm, clip_norm_max, always_clip ? 1 : 0, out);
+  PASSL_RETURN_IF_LAUNCH_FAILED();
+  return PASSL_OK;
+}

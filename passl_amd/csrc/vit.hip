@@ -519,16 +519,20 @@ __global__ void __launch_bounds__(kThreads) ordered_sum_kernel(const float* __re
 // The derived scalars and the element update, stated ONCE: the flat and the grouped kernel both call this, so a
 // segment updated with (lr*scale, wd_s) gets the bits the flat kernel gives a buffer of its own with those two values
 // (correctly rounded sqrt / divide: also the bits the host would compute).
+// kClip (global-norm gradient clipping): the scaled gradient times the set's coefficient, gg = (g*gs)*coef — nothing else.
+template <bool kClip = false>
 __device__ __forceinline__ void adamw_update(float* __restrict__ pp, const float* __restrict__ gp,
                                              float* __restrict__ mp, float* __restrict__ vp, int count, float lr,
-                                             float wd, float b1p, float b2p, float eps, float b1, float b2, float gs) {
+                                             float wd, float b1p, float b2p, float eps, float b1, float b2, float gs,
+                                             float coef = 1.f) {
   const float c2 = sqrtf(1.f - b2p);
   const float decay = 1.f - lr * wd;
   const float lr_t = lr * c2 / (1.f - b1p);
   const float eps_t = eps * c2;
 #pragma unroll
   for (int e = 0; e < count; ++e) {
-    const float gg = gp[e] * gs;
+    float gg = gp[e] * gs;
+    if (kClip) gg *= coef;
     mp[e] = b1 * mp[e] + (1.f - b1) * gg;
     vp[e] = b2 * vp[e] + (1.f - b2) * gg * gg;
     pp[e] = pp[e] * decay - lr_t * (mp[e] / (sqrtf(vp[e]) + eps_t));
@@ -595,6 +599,65 @@ __global__ void __launch_bounds__(kThreads) adamw_groups_kernel(
     float4 mv = reinterpret_cast<float4*>(m)[i];
     float4 vv = reinterpret_cast<float4*>(v)[i];
     adamw_update(&pv.x, &gv.x, &mv.x, &vv.x, 4, lr_s, wd_s, b1p, b2p, eps, b1, b2, gs);
+    reinterpret_cast<float4*>(p)[i] = pv;
+    reinterpret_cast<float4*>(m)[i] = mv;
+    reinterpret_cast<float4*>(v)[i] = vv;
+  }
+}
+
+// The clip variants: the same walks, the gradient times a coefficient that grad_clip_finalize_kernel (flat.hip) left in
+// device memory.  Flat: one coefficient.  Grouped: clip = the {norm, coef} table, seg_set[s] the set of segment s
+// (outside [0, n_sets): coefficient 1 — a parameter excluded from clipping).  n % 4 == 0 for both.
+__global__ void __launch_bounds__(kThreads) adamw_clip_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                              float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                              const float* __restrict__ hyper,
+                                                              const float* __restrict__ coef_p, float wd, float eps,
+                                                              float b1, float b2, float gs) {
+  const float lr = hyper[0], b1p = hyper[1], b2p = hyper[2];
+  const float coef = coef_p[0];
+  const int64_t nv = n >> 2;
+  const int64_t stride = (int64_t)gridDim.x * kThreads;
+  for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < nv; i += stride) {
+    float4 pv = reinterpret_cast<float4*>(p)[i];
+    const float4 gv = reinterpret_cast<const float4*>(g)[i];
+    float4 mv = reinterpret_cast<float4*>(m)[i];
+    float4 vv = reinterpret_cast<float4*>(v)[i];
+    adamw_update<true>(&pv.x, &gv.x, &mv.x, &vv.x, 4, lr, wd, b1p, b2p, eps, b1, b2, gs, coef);
+    reinterpret_cast<float4*>(p)[i] = pv;
+    reinterpret_cast<float4*>(m)[i] = mv;
+    reinterpret_cast<float4*>(v)[i] = vv;
+  }
+}
+
+__global__ void __launch_bounds__(kThreads) adamw_groups_clip_kernel(
+    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
+    const int64_t* __restrict__ seg_end, const float* __restrict__ seg_lr_scale, const float* __restrict__ seg_wd,
+    const int32_t* __restrict__ seg_set, int n_seg, const float* __restrict__ hyper, const float* __restrict__ clip,
+    int n_sets, float eps, float b1, float b2, float gs) {
+  const float lr = hyper[0], b1p = hyper[1], b2p = hyper[2];
+  const int64_t nv = n >> 2;
+  const int64_t stride = (int64_t)gridDim.x * kThreads;
+  int s0 = 0;
+  for (int64_t tile = (int64_t)blockIdx.x * kThreads; tile < nv; tile += stride) {
+    const int64_t first = tile << 2;
+    int hi = n_seg - 1;
+    while (s0 < hi) {
+      const int mid = (s0 + hi) >> 1;
+      if (first < seg_end[mid]) hi = mid; else s0 = mid + 1;
+    }
+    const int64_t i = tile + threadIdx.x;
+    if (i >= nv) continue;
+    int s = s0;
+    while (s + 1 < n_seg && (i << 2) >= seg_end[s]) ++s;
+    const float lr_s = lr * seg_lr_scale[s];
+    const float wd_s = seg_wd[s];
+    const int set = seg_set[s];
+    const float coef = (set >= 0 && set < n_sets) ? clip[2 * set + 1] : 1.f;
+    float4 pv = reinterpret_cast<float4*>(p)[i];
+    const float4 gv = reinterpret_cast<const float4*>(g)[i];
+    float4 mv = reinterpret_cast<float4*>(m)[i];
+    float4 vv = reinterpret_cast<float4*>(v)[i];
+    adamw_update<true>(&pv.x, &gv.x, &mv.x, &vv.x, 4, lr_s, wd_s, b1p, b2p, eps, b1, b2, gs, coef);
     reinterpret_cast<float4*>(p)[i] = pv;
     reinterpret_cast<float4*>(m)[i] = mv;
     reinterpret_cast<float4*>(v)[i] = vv;
@@ -892,6 +955,43 @@ extern "C" int passl_hip_adamw_groups_dev(float* p, const float* g, float* m, fl
   if (b > 2048) b = 2048;
   hipLaunchKernelGGL(adamw_groups_kernel, dim3((unsigned)b), dim3(kThreads), 0, as_stream(stream), p, g, m, v, n,
                      seg_end, seg_lr_scale, seg_wd, n_seg, hyper, epsilon, beta1, beta2, grad_scale);
+  PASSL_RETURN_IF_LAUNCH_FAILED();
+  return PASSL_OK;
+}
+
+extern "C" int passl_hip_adamw_clip_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper,
+                                        const float* coef, float beta1, float beta2, float epsilon,
+                                        float weight_decay, float grad_scale, passl_stream_t stream) {
+  if (!p || !g || !m || !v || !hyper || !coef || n < 0 || (n & 3) || !aligned16(p) || !aligned16(g) ||
+      !aligned16(m) || !aligned16(v) || (reinterpret_cast<uintptr_t>(hyper) & 3u) ||
+      (reinterpret_cast<uintptr_t>(coef) & 3u))
+    return PASSL_EINVAL;
+  if (n == 0) return PASSL_OK;
+  int64_t b = ((n >> 2) + kThreads - 1) / kThreads;       // the flat kernel's grid
+  if (b > 2048) b = 2048;
+  hipLaunchKernelGGL(adamw_clip_kernel, dim3((unsigned)b), dim3(kThreads), 0, as_stream(stream), p, g, m, v, n,
+                     hyper, coef, weight_decay, epsilon, beta1, beta2, grad_scale);
+  PASSL_RETURN_IF_LAUNCH_FAILED();
+  return PASSL_OK;
+}
+
+extern "C" int passl_hip_adamw_groups_clip_dev(float* p, const float* g, float* m, float* v, int64_t n,
+                                               const int64_t* seg_end, const float* seg_lr_scale,
+                                               const float* seg_wd, const int32_t* seg_set, int n_seg,
+                                               const float* hyper, const float* clip, int n_sets, float beta1,
+                                               float beta2, float epsilon, float grad_scale, passl_stream_t stream) {
+  if (!p || !g || !m || !v || !hyper || !clip || !seg_end || !seg_lr_scale || !seg_wd || !seg_set || n < 0 ||
+      (n & 3) || n_seg <= 0 || n_sets <= 0 || !aligned16(p) || !aligned16(g) || !aligned16(m) || !aligned16(v) ||
+      (reinterpret_cast<uintptr_t>(seg_end) & 7u) || (reinterpret_cast<uintptr_t>(seg_lr_scale) & 3u) ||
+      (reinterpret_cast<uintptr_t>(seg_wd) & 3u) || (reinterpret_cast<uintptr_t>(seg_set) & 3u) ||
+      (reinterpret_cast<uintptr_t>(hyper) & 3u) || (reinterpret_cast<uintptr_t>(clip) & 3u))
+    return PASSL_EINVAL;
+  if (n == 0) return PASSL_OK;
+  int64_t b = ((n >> 2) + kThreads - 1) / kThreads;
+  if (b > 2048) b = 2048;
+  hipLaunchKernelGGL(adamw_groups_clip_kernel, dim3((unsigned)b), dim3(kThreads), 0, as_stream(stream), p, g, m, v, n,
+                     seg_end, seg_lr_scale, seg_wd, seg_set, n_seg, hyper, clip, n_sets, epsilon, beta1, beta2,
+                     grad_scale);
   PASSL_RETURN_IF_LAUNCH_FAILED();
   return PASSL_OK;
 }

@@ -28,6 +28,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from ..core.grad_clip import build_grad_clip
 from ..core.sync_utils import GradReducer, ReducerGroup, collectives_active, param_sync
 from ..hip import config as hip_config
 from ..models import build_model
@@ -307,9 +308,14 @@ class Engine(object):
         # do not implement: say so by name instead of a TypeError from the constructor.  `tensor_fusion` asks Paddle to
         # fuse parameter storage — the arena IS fused storage, nothing to do.
         opt_cfg.pop('tensor_fusion', None)
-        if opt_cfg.get('grad_clip', None) is None:
-            opt_cfg.pop('grad_clip', None)
-        for k in ('grad_clip', 'no_weight_decay_name', 'layer_decay'):
+        # grad_clip: {name: ClipGradByGlobalNorm, clip_norm: ...} builds the configuration object (core/grad_clip.py; name
+        # defaults to ClipGradByGlobalNorm, passl/optimizer/__init__.py:130-133) for AdamW, the one optimizer that clips
+        grad_clip = opt_cfg.pop('grad_clip', None)
+        if grad_clip not in (None, [], '', {}):
+            if klass is not OPTIMIZERS.get('AdamW'):
+                raise NotImplementedError('Optimizer.grad_clip is built for AdamW only, not for %s' % name)
+            opt_cfg['grad_clip'] = build_grad_clip(grad_clip)
+        for k in ('no_weight_decay_name', 'layer_decay'):
             if opt_cfg.get(k, None) not in (None, [], ''):
                 raise NotImplementedError('Optimizer.%s is not built on the HIP path (pre-training recipes of '
                                           'tasks/ssl do not use it)' % k)

@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(os.path.dirname(_HERE), 'lib', 'libpassl_hip.so')
 
 F32, BF16 = 0, 1
 ABI_VERSION = 16          # include/passl_hip.h: PASSL_HIP_ABI_VERSION (the ctypes structs below mirror THAT layout)
+GRAD_CLIP_CHUNK = 16384   # include/passl_hip.h: PASSL_GRAD_CLIP_CHUNK (load() checks the library against it)
 _DT = {torch.float32: F32, torch.bfloat16: BF16}
 
 c_p = C.c_void_p
@@ -163,6 +164,12 @@ SIGNATURES = {
     'passl_hip_adamw': (c_i, [c_p, c_p, c_p, c_p, c_l, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_p]),
     'passl_hip_adamw_dev': (c_i, [c_p, c_p, c_p, c_p, c_l, c_p, c_f, c_f, c_f, c_f, c_f, c_p]),
     'passl_hip_adamw_groups_dev': (c_i, [c_p, c_p, c_p, c_p, c_l, c_p, c_p, c_p, c_i, c_p, c_f, c_f, c_f, c_f, c_p]),
+    'passl_hip_grad_clip_chunk': (c_i, [c_i]),
+    'passl_hip_grad_sumsq': (c_i, [c_p, c_l, c_p, c_p, c_i, c_f, c_p, c_p]),
+    'passl_hip_grad_clip_finalize': (c_i, [c_p, c_i, c_p, c_p, c_i, c_i, c_f, c_f, c_i, c_p, c_p]),
+    'passl_hip_adamw_clip_dev': (c_i, [c_p, c_p, c_p, c_p, c_l, c_p, c_p, c_f, c_f, c_f, c_f, c_f, c_p]),
+    'passl_hip_adamw_groups_clip_dev': (c_i, [c_p, c_p, c_p, c_p, c_l, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_f, c_f,
+                                              c_f, c_f, c_p]),
     'passl_hip_cosine_loss_fwd': (c_i, [c_p, c_p, c_i, c_i, c_f, c_p, c_p, c_p]),
     'passl_hip_cosine_loss_bwd': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p]),
     'passl_hip_softmax_ce_fwd': (c_i, [c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_l, c_p]),
@@ -214,6 +221,9 @@ def load(path=None):
         fn = getattr(lib, name)          # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
+    if lib.passl_hip_grad_clip_chunk(ABI_VERSION) != GRAD_CLIP_CHUNK:
+        raise PasslHipError('%s clips gradients in chunks of %d, this binding expects %d: rebuild it'
+                            % (p, lib.passl_hip_grad_clip_chunk(ABI_VERSION), GRAD_CLIP_CHUNK))
     if path is None:
         _lib = lib
         # wgrad_halo is ONE switch with two readers (the library's kernel choice, config's slice count): Python's value

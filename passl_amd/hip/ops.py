@@ -952,6 +952,128 @@ def adamw_groups_dev(p, g, m, v, table, hyper, b1, b2, eps, grad_scale=1.0):
                                               L.ptr(hyper), b1, b2, eps, grad_scale, L.stream()), 'adamw_groups_dev')
 
 
+# ---- global-norm gradient clipping (include/passl_hip.h "global-norm gradient clipping")
+GRAD_CLIP_CHUNK = L.GRAD_CLIP_CHUNK
+
+
+def grad_clip_plan(runs, sizes, n_sets, device):
+    """The chunk tables and the CSR index of passl_hip_grad_sumsq / passl_hip_grad_clip_finalize, built and validated
+    HERE, once, on the host (the kernels only keep their accesses in bounds).  ``runs``: per gradient buffer a list of
+    (start, end, set) — ascending, disjoint element ranges [start, end) with offsets that are multiples of 4, each inside
+    the buffer of ``sizes[b]`` elements and belonging to ONE set in [0, n_sets); what no run covers is in no norm.  Every
+    run is tiled by chunks of at most GRAD_CLIP_CHUNK elements, so no chunk crosses a run.  Chunks are numbered buffer
+    after buffer (``base[b]`` = the first chunk of buffer b in the one partial buffer); a set's chunks are listed in
+    ascending number.  -> dict: per-buffer device tables chunk_off (int64) / chunk_len (int32), base, n_chunks; set_ptr /
+    set_chunks (int32), partial (total floats), out ([n_sets, 2] = {norm, coef}); ``host``: the same tables as lists."""
+    n_sets = int(n_sets)
+    if n_sets <= 0 or len(runs) != len(sizes):
+        raise ValueError('grad_clip_plan: %d sets, %d run lists for %d buffers' % (n_sets, len(runs), len(sizes)))
+    offs, lens, sets_of = [], [], []
+    for b, (rs, n) in enumerate(zip(runs, sizes)):
+        n = int(n)
+        if n % 4:
+            raise ValueError('grad_clip_plan: buffer %d holds %d elements, not a multiple of 4' % (b, n))
+        o, l, k = [], [], []
+        prev = 0
+        for start, end, st in rs:
+            start, end, st = int(start), int(end), int(st)
+            if start % 4 or end % 4 or not prev <= start < end <= n:
+                raise ValueError('grad_clip_plan: buffer %d: run [%d, %d) after %d in a buffer of %d elements (ascending, '
+                                 'disjoint, multiples of 4 wanted)' % (b, start, end, prev, n))
+            if not 0 <= st < n_sets:
+                raise ValueError('grad_clip_plan: buffer %d: run [%d, %d) names set %d of %d' % (b, start, end, st, n_sets))
+            for c in range(start, end, GRAD_CLIP_CHUNK):
+                o.append(c)
+                l.append(min(GRAD_CLIP_CHUNK, end - c))
+                k.append(st)
+            prev = end
+        offs.append(o)
+        lens.append(l)
+        sets_of.append(k)
+    base, total = [], 0
+    for o in offs:
+        base.append(total)
+        total += len(o)
+    if total == 0:
+        raise ValueError('grad_clip_plan: no run at all — nothing to clip')
+    if total >= 2 ** 31:
+        raise ValueError('grad_clip_plan: %d chunks do not fit an int32 index' % total)
+    members = [[] for _ in range(n_sets)]
+    for b, k in enumerate(sets_of):
+        for i, st in enumerate(k):
+            members[st].append(base[b] + i)
+    set_ptr, set_chunks = [0], []
+    for mm in members:
+        set_chunks += mm
+        set_ptr.append(len(set_chunks))
+    assert sorted(set_chunks) == list(range(total))
+    host = dict(chunk_off=offs, chunk_len=lens, chunk_set=sets_of, base=base, set_ptr=set_ptr, set_chunks=set_chunks)
+    return dict(chunk_off=[torch.tensor(o, dtype=torch.int64, device=device) for o in offs],
+                chunk_len=[torch.tensor(l, dtype=torch.int32, device=device) for l in lens],
+                base=base, n_chunks=[len(o) for o in offs], sizes=[int(n) for n in sizes], total=total,
+                set_ptr=torch.tensor(set_ptr, dtype=torch.int32, device=device),
+                set_chunks=torch.tensor(set_chunks, dtype=torch.int32, device=device), n_sets=n_sets,
+                partial=torch.zeros(total, dtype=torch.float32, device=device),
+                out=torch.zeros(n_sets, 2, dtype=torch.float32, device=device), host=host)
+
+
+def grad_sumsq(g, plan, b, grad_scale=1.0):
+    """partial[base[b] + c] = sum of fp32(g*grad_scale)^2 over chunk c of gradient buffer b (nothing to do for a buffer
+    without chunks)."""
+    if plan['sizes'][b] != g.numel():
+        raise ValueError('grad_sumsq: the plan covers %d elements of buffer %d, it holds %d' % (plan['sizes'][b], b, g.numel()))
+    nc = plan['n_chunks'][b]
+    if nc == 0:
+        return
+    L.check(_lib().passl_hip_grad_sumsq(L.ptr(g), g.numel(), L.ptr(plan['chunk_off'][b]), L.ptr(plan['chunk_len'][b]), nc,
+                                        grad_scale, L.ptr(plan['partial'][plan['base'][b]:]), L.stream()), 'grad_sumsq')
+
+
+def grad_clip_finalize(plan, clip_norm, clip_norm_max=None, always_clip=False):
+    """plan['out'][s] = {norm, coef} of every set from the partials, by the rule of ClipGradByGlobalNorm."""
+    L.check(_lib().passl_hip_grad_clip_finalize(L.ptr(plan['partial']), plan['total'], L.ptr(plan['set_ptr']),
+                                                L.ptr(plan['set_chunks']), plan['total'], plan['n_sets'], clip_norm,
+                                                float('inf') if clip_norm_max is None else clip_norm_max,
+                                                1 if always_clip else 0, L.ptr(plan['out']), L.stream()),
+            'grad_clip_finalize')
+    return plan['out']
+
+
+def adamw_clip_dev(p, g, m, v, hyper, coef, b1, b2, eps, wd, grad_scale=1.0):
+    """adamw_dev with the gradient times coef[0] (a device float, e.g. plan['out'][s, 1:]): gg = (g*grad_scale)*coef."""
+    L.check(_lib().passl_hip_adamw_clip_dev(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), p.numel(), L.ptr(hyper), L.ptr(coef),
+                                            b1, b2, eps, wd, grad_scale, L.stream()), 'adamw_clip_dev')
+
+
+def adamw_groups_clip_table(seg_end, seg_lr_scale, seg_wd, seg_set, n, n_sets, device):
+    """adamw_groups_table + the set of every segment (-1: not clipped), validated on the host."""
+    sets = [int(x) for x in seg_set]
+    if len(sets) != len(seg_end):
+        raise ValueError('adamw_groups_clip_table: %d ends, %d sets' % (len(seg_end), len(sets)))
+    for i, st in enumerate(sets):
+        if not -1 <= st < int(n_sets):
+            raise ValueError('adamw_groups_clip_table: segment %d names set %d of %d (-1: not clipped)' % (i, st, n_sets))
+    table = adamw_groups_table(seg_end, seg_lr_scale, seg_wd, n, device)
+    table['seg_set'] = torch.tensor(sets, dtype=torch.int32, device=device)
+    table['n_sets'] = int(n_sets)
+    return table
+
+
+def adamw_groups_clip_dev(p, g, m, v, table, hyper, clip, b1, b2, eps, grad_scale=1.0):
+    """adamw_groups_dev with the gradient of segment s times clip[seg_set[s], 1] (``clip``: the [n_sets, 2] table of
+    grad_clip_finalize; ``table``: adamw_groups_clip_table)."""
+    if table['n'] != p.numel():
+        raise ValueError('adamw_groups_clip_dev: the table covers %d elements, the buffer holds %d' % (table['n'], p.numel()))
+    if clip.numel() != 2 * table['n_sets']:
+        raise ValueError('adamw_groups_clip_dev: the table names %d sets, the coefficient table holds %d'
+                         % (table['n_sets'], clip.numel() // 2))
+    L.check(_lib().passl_hip_adamw_groups_clip_dev(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), p.numel(),
+                                                   L.ptr(table['seg_end']), L.ptr(table['seg_lr_scale']),
+                                                   L.ptr(table['seg_wd']), L.ptr(table['seg_set']), table['n_seg'],
+                                                   L.ptr(hyper), L.ptr(clip), table['n_sets'], b1, b2, eps, grad_scale,
+                                                   L.stream()), 'adamw_groups_clip_dev')
+
+
 # ------------------------------------------------------------------ CLIP
 def quick_gelu_fwd(x):
     y = torch.empty_like(x)

@@ -10,6 +10,7 @@ passl/optimizer/momentum.py:150-158.
 import torch
 
 from ..hip import ops, streams
+from ..core.grad_clip import ClipGradByGlobalNorm
 from .builder import OPTIMIZERS
 from .lr_scheduler import LRScheduler
 
@@ -384,8 +385,9 @@ class AdamW(_DeviceHyper):
             beta1, beta2 = (float(b) for b in betas)
         if eps is not None:
             epsilon = eps
-        if grad_clip is not None:
-            raise NotImplementedError('gradient clipping is not built')
+        if grad_clip is not None and not isinstance(grad_clip, ClipGradByGlobalNorm):
+            raise NotImplementedError('grad_clip: only core.grad_clip.ClipGradByGlobalNorm is built, got %r'
+                                      % (type(grad_clip).__name__,))
         self._learning_rate = learning_rate
         self._b1, self._b2, self._eps = float(beta1), float(beta2), float(epsilon)
         self._wd = float(weight_decay) if weight_decay else 0.0
@@ -407,14 +409,14 @@ class AdamW(_DeviceHyper):
                 wd = self._wd if wd is None else float(wd)
                 if wd < 0:
                     raise ValueError('parameter group %d: weight_decay must be >= 0, got %r' % (gi, wd))
-                listed += [(p, scale, wd) for p in group['params'] if p.requires_grad]
+                listed += [(p, scale, wd, gi) for p in group['params'] if p.requires_grad]
         elif any(isinstance(g, dict) for g in parameters):
             raise ValueError('parameters: a list of tensors or a list of group dicts, not a mixture')
         else:
-            listed = [(p, 1.0, self._wd) for p in parameters if p.requires_grad]
+            listed = [(p, 1.0, self._wd, 0) for p in parameters if p.requires_grad]
         arenas = []
         seen = {}
-        for p, _s, _w in listed:
+        for p, _s, _w, _g in listed:
             a = getattr(p, '_passl_arena', None)
             if a is None:
                 raise NotImplementedError('AdamW optimises parameters that live in an EncoderArena')
@@ -424,42 +426,82 @@ class AdamW(_DeviceHyper):
             if a not in arenas:
                 arenas.append(a)
         for a in arenas:
-            if sum(1 for p, _s, _w in listed if p._passl_arena is a) != len(a.param_slices):
+            if sum(1 for p, _s, _w, _g in listed if p._passl_arena is a) != len(a.param_slices):
                 raise NotImplementedError('optimising a subset of an arena is not supported')
-        self._parameter_list = [p for p, _s, _w in listed]
+        self._parameter_list = [p for p, _s, _w, _g in listed]
         self._arenas = arenas
         self._param_table = []         # per arena: [(paddle auto-name, multiplier, decay)] in arena order
         self._tables = []              # per arena: None (flat kernel with _flat_wd) or the device table
         self._flat_wd = []
+        # clipping (core/grad_clip.py): the set of every parameter — its group ('group' scope; a plain list is group 0)
+        # or 0 ('global'), -1 when the parameter is left out — then per arena the runs of equal set for the chunk table
+        self._grad_clip = grad_clip
+        self._clip = None              # ops.grad_clip_plan over all arenas, or None: nothing is clipped
+        self._clip_coef = []           # per arena: the device float of its one set (flat clip launch) or None
+        n_sets = 1 if grad_clip is None or grad_clip.scope == 'global' else max([g for _p, _s, _w, g in listed] + [0]) + 1
+        param_sets, runs = [], []
         for a in arenas:
             names = _paddle_auto_names(a)
             assert len(names) == len(a.param_slices)
             rows = [None] * len(names)
-            for p, scale, wd in listed:
+            sets = [-1] * len(names)
+            for p, scale, wd, gi in listed:
                 if p._passl_arena is not a:
                     continue
                 name = names[p._passl_index]
+                if grad_clip is not None and not grad_clip.excludes(p, name):
+                    sets[p._passl_index] = 0 if grad_clip.scope == 'global' else gi
                 if lr_ratio is not None:
                     scale = scale * float(lr_ratio(p))
                 if apply_decay_param_fun is not None and not apply_decay_param_fun(name):
                     wd = 0.0
                 rows[p._passl_index] = (name, scale, wd)
             self._param_table.append(rows)
-            if all(s == 1.0 for _n, s, _w in rows) and len({w for _n, _s, w in rows}) == 1:
+            param_sets.append(sets)
+            ends = [off for off, _n in a.param_slices[1:]] + [a.n_train]
+            starts = [off for off, _n in a.param_slices]
+            run = []
+            for start, end, st in zip(starts, ends, sets):
+                if st < 0:
+                    continue
+                if run and run[-1][1] == start and run[-1][2] == st:
+                    run[-1] = (run[-1][0], end, st)
+                else:
+                    run.append((start, end, st))
+            runs.append(run)
+        if grad_clip is not None and any(runs):
+            self._clip = ops.grad_clip_plan(runs, [a.n_train for a in arenas], n_sets,
+                                            arenas[0].device if arenas else torch.device('cpu'))
+        self._param_sets = param_sets
+        for a, rows, sets in zip(arenas, self._param_table, param_sets):
+            one_set = len(set(sets)) == 1
+            if self._clip is not None and one_set and sets[0] < 0:
+                sets = None                                  # nothing of this arena is clipped: today's launches
+            if self._clip is None:
+                sets = None
+            if all(s == 1.0 for _n, s, _w in rows) and len({w for _n, _s, w in rows}) == 1 \
+                    and (sets is None or one_set):
                 self._tables.append(None)
                 self._flat_wd.append(rows[0][2])
+                self._clip_coef.append(None if sets is None else self._clip['out'][sets[0], 1:])
                 continue
             ends = [off for off, _n in a.param_slices[1:]] + [a.n_train]
-            seg_end, seg_scale, seg_wd = [], [], []
-            for end, (_name, scale, wd) in zip(ends, rows):
-                if seg_end and (seg_scale[-1], seg_wd[-1]) == (scale, wd):
+            seg_end, seg_scale, seg_wd, seg_set = [], [], [], []
+            for end, (_name, scale, wd), st in zip(ends, rows, sets or [-1] * len(rows)):
+                if seg_end and (seg_scale[-1], seg_wd[-1], seg_set[-1]) == (scale, wd, st):
                     seg_end[-1] = end
                 else:
                     seg_end.append(end)
                     seg_scale.append(scale)
                     seg_wd.append(wd)
-            self._tables.append(ops.adamw_groups_table(seg_end, seg_scale, seg_wd, a.n_train, a.device))
+                    seg_set.append(st)
+            if sets is None:
+                self._tables.append(ops.adamw_groups_table(seg_end, seg_scale, seg_wd, a.n_train, a.device))
+            else:
+                self._tables.append(ops.adamw_groups_clip_table(seg_end, seg_scale, seg_wd, seg_set, a.n_train,
+                                                                self._clip['n_sets'], a.device))
             self._flat_wd.append(None)
+            self._clip_coef.append(None)
         self._m = [torch.zeros_like(a.flat[:a.n_train]) for a in arenas]
         self._v = [torch.zeros_like(a.flat[:a.n_train]) for a in arenas]
         self._t = 0
@@ -493,6 +535,8 @@ class AdamW(_DeviceHyper):
     @torch.no_grad()
     def step(self):
         hyper = self._hyper_for_step()
+        if self._clip is not None:
+            return self._step_clipped(hyper)
         for a, m, v, table, wd in zip(self._arenas, self._m, self._v, self._tables, self._flat_wd):
             _grads_complete(a)
             if table is None:
@@ -501,6 +545,37 @@ class AdamW(_DeviceHyper):
             else:
                 ops.adamw_groups_dev(a.flat[:a.n_train], a.grads, m, v, table, hyper, self._b1, self._b2, self._eps,
                                      self.grad_scale)
+
+    def _step_clipped(self, hyper):
+        """Every arena's gradients complete, then: the chunk sums (one launch per arena), one finalize for all sets, the
+        updates.  Nothing comes back to the host: the coefficients are read by the update kernels from device memory."""
+        clip, gc = self._clip, self._grad_clip
+        for a in self._arenas:
+            _grads_complete(a)
+        for b, a in enumerate(self._arenas):
+            ops.grad_sumsq(a.grads, clip, b, self.grad_scale)
+        ops.grad_clip_finalize(clip, gc.clip_norm, gc.clip_norm_max, gc.always_clip)
+        for a, m, v, table, wd, coef in zip(self._arenas, self._m, self._v, self._tables, self._flat_wd, self._clip_coef):
+            p = a.flat[:a.n_train]
+            if table is None and coef is None:
+                ops.adamw_dev(p, a.grads, m, v, hyper, self._b1, self._b2, self._eps, wd, self.grad_scale)
+            elif table is None:
+                ops.adamw_clip_dev(p, a.grads, m, v, hyper, coef, self._b1, self._b2, self._eps, wd, self.grad_scale)
+            elif 'seg_set' not in table:
+                ops.adamw_groups_dev(p, a.grads, m, v, table, hyper, self._b1, self._b2, self._eps, self.grad_scale)
+            else:
+                ops.adamw_groups_clip_dev(p, a.grads, m, v, table, hyper, clip['out'], self._b1, self._b2, self._eps,
+                                          self.grad_scale)
+
+    def grad_norms(self):
+        """The device table [n_sets, 2] = {norm, coef} of the last step's sets (set = parameter group under the 'group'
+        scope, one set under 'global'), without synchronising: a caller who logs it reads it when it likes.  None without
+        clipping."""
+        return None if self._clip is None else self._clip['out']
+
+    def clip_sets(self):
+        """[(name, set)] of every parameter in arena order; set -1 = left out of clipping (or no clipping at all)."""
+        return [(row[0], st) for rows, sets in zip(self._param_table, self._param_sets) for row, st in zip(rows, sets)]
 
     def state_dict(self):
         sd = {'t': self._t}
