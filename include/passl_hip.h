@@ -702,6 +702,31 @@ int passl_hip_soft_ce_fwd(const float* scores, const float* target, int N, int C
 int passl_hip_soft_ce_bwd(const float* scores, const float* target, const float* lse, const float* tsum,
                           const float* gloss, int N, int C, float* dscores, passl_stream_t stream);
 
+/* ---------------------------------------------------------------- random erasing
+ * Reference: class RandomErasing, passl_v110/datasets/preprocess/random_erasing.py:34-115 (it erases on the host, sample
+ * by sample).  x, out fp32 NCHW [B,C,H,W]; boxes: a DEVICE table int32 [B][4] = (top, left, h, w), h == 0 or w == 0
+ * meaning "this sample is not erased".  One row per sample is the whole interface: the reference erases at most one box
+ * per sample whatever max_count is (`_erase` returns after its first successful box, :89-103; the drawn count only
+ * divides the target area).
+ *   out != x: out of place, one pass; out = x outside the box and the fill inside it, x is never written.
+ *   out == x: in place; only box elements are stored, x is not loaded.  (Buffers that overlap otherwise: undefined
+ *     values, no access outside them.)
+ *   mode 0 ('const'): the fill is 0.0f.
+ *   mode 1 ('pixel'): the fill is a standard normal defined by position.  e = (c*H + y)*W + x_col (the element's index
+ *     inside its sample), g = e >> 2, (w0,w1,w2,w3) = Philox4x32-10(counter (g, b, step_lo32, step_hi32), key (seed_lo32,
+ *     seed_hi32)); u0 = (float(w0 >> 8) + 1) * 2^-24 and u2 likewise from w2, in (0, 1]; u1 = float(w1 >> 8) * 2^-24 and
+ *     u3 likewise from w3, in [0, 1); r01 = sqrtf(-2 logf(u0)), r23 = sqrtf(-2 logf(u2));
+ *     z = (r01 cos 2 pi u1, r01 sin 2 pi u1, r23 cos 2 pi u3, r23 sin 2 pi u3); element e gets z[e & 3].  Precise
+ *     single-precision logf / sqrtf / sincospif.  A sample's values depend on (seed, step, b, e) only: not on B, not on
+ *     the grid, not on the box.
+ *   The reference's 'rand' mode (one colour per box) is not built: its class raises on any box whose width is not 3.
+ * 16-byte accesses when C*H*W % 4 == 0 and both pointers are 16-byte aligned, single floats otherwise.  The library
+ * cannot read the table on the host: the caller validates it; the kernel clamps every box to the image, so no access
+ * leaves the tensor whatever the table holds.  NULL pointers, B < 0, C, H, W <= 0, C*H*W >= 2^31, an unknown mode,
+ * pointers not 4-byte aligned -> PASSL_EINVAL; B == 0 -> PASSL_OK, nothing launched. */
+int passl_hip_random_erase(const float* x, float* out, const int32_t* boxes, int B, int C, int H, int W, int mode,
+                           int64_t seed, int64_t step, passl_stream_t stream);
+
 /* ---------------------------------------------------------------- measurement hooks */
 
 /* When enabled, every passl_hip_conv_igemm / passl_hip_conv_wgrad launch is bracketed by HIP

@@ -16,15 +16,19 @@ def build_dataset(cfg):
 def build_dataloader(cfg, device):
     """cfg = dataloader.train block: {loader, sampler, dataset}.  Returns (loader, mixup_fn): ``dataset.batch_transforms``
     is popped as the reference does (builder.py:88-103) and built by preprocess.build_mixup — a Mixup when the block
-    mixes, else None.  The Trainer hands it to every model call; only the train block's is used."""
-    from .preprocess import build_mixup
-    from .synthetic import SyntheticLoader
+    mixes, else None.  The Trainer hands it to every model call; only the train block's is used.
+    A ``RandomErasing`` entry of ``dataset.transforms`` (preprocess.build_random_erasing) of a SyntheticLabeled source
+    becomes the loader's ``batch_transform``: erasing happens in the loader, i.e. before ``mixup_fn`` — the reference's
+    order, per-sample transform first, then the collate-time mix.  Every other entry stays ignored."""
+    from .preprocess import build_mixup, build_random_erasing
+    from .synthetic import SyntheticLabeled, SyntheticLoader
     ds_cfg = dict(cfg['dataset'])
     mixup_cfg = ds_cfg.pop('batch_transforms', None)
     sampler = cfg.get('sampler', {})
     dataset = build_dataset(ds_cfg)
+    eraser = build_random_erasing(ds_cfg.get('transforms', None)) if isinstance(dataset, SyntheticLabeled) else None
     loader = SyntheticLoader(dataset, batch_size=sampler.get('batch_size', 32), device=device,
-                             drop_last=sampler.get('drop_last', True))
+                             drop_last=sampler.get('drop_last', True), batch_transform=eraser)
     ring = int((cfg.get('loader', None) or {}).get('host_ring', 0) or 0)
     if ring:
         from .synthetic import HostRingLoader

@@ -121,8 +121,13 @@ class ImageFolder(object):
 
 
 class SyntheticLoader(object):
-    def __init__(self, dataset, batch_size, device, drop_last=True):
+    """``batch_transform``: a callable applied OUT OF PLACE to the image tensor of every (image, label) batch that is
+    yielded (preprocess.RandomErasing: the per-sample transform of the reference's pipeline that can run on a resident
+    batch); the cached batch itself stays bit-unchanged.  None: batches are yielded as they are cached."""
+
+    def __init__(self, dataset, batch_size, device, drop_last=True, batch_transform=None):
         self.dataset = dataset
+        self.batch_transform = batch_transform
         self.batch_size = int(batch_size)
         self.device = device
         world = int(os.environ.get('WORLD_SIZE', 1))
@@ -151,6 +156,8 @@ class SyntheticLoader(object):
             b = self._cache[i % len(self._cache)]
             if self._tail and i == n - 1 and self._len > 0:
                 b = tuple(t[:self._tail] for t in b)
+            if self.batch_transform is not None:
+                b = (self.batch_transform(b[0]),) + tuple(b[1:])
             yield b
 
 
@@ -177,6 +184,7 @@ class HostRingLoader(object):
         self.dataset = inner.dataset
         self.batch_size = inner.batch_size
         self.device = inner.device
+        self.batch_transform = getattr(inner, 'batch_transform', None)   # applied to what take() hands out
         self._len = len(inner)
         rank = int(os.environ.get('RANK', 0))
         gen = torch.Generator().manual_seed(inner.dataset.seed + rank)
@@ -219,7 +227,7 @@ class HostRingLoader(object):
         if not self._cuda:
             b = self._host[self._taken % len(self._host)]
             self._taken += 1
-            return b
+            return self._transformed(b)
         cur = torch.cuda.current_stream(self.device)
         if self._taken > 0:
             # everything enqueued so far has read the slot handed out LAST time (the step that consumed it)
@@ -229,7 +237,12 @@ class HostRingLoader(object):
         slot = self._taken % self.SLOTS
         cur.wait_event(self._ready[slot])
         self._taken += 1
-        return self._slots[slot]
+        return self._transformed(self._slots[slot])
+
+    def _transformed(self, b):
+        if self.batch_transform is None:
+            return b
+        return (self.batch_transform(b[0]),) + tuple(b[1:])          # out of place, on the compute stream
 
     def __iter__(self):
         for _ in range(len(self)):

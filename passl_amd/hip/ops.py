@@ -862,6 +862,26 @@ def mixup_target(labels, num_classes, lam=1.0, eps=0.0):
     return target
 
 
+# ------------------------------------------------------------------ random erasing (csrc/random_erasing.hip)
+def random_erase(x, boxes, mode, seed, step, out=None):
+    """x fp32 NCHW [B,C,H,W]; boxes int32 [B,4] = (top, left, h, w) on the device, h == 0 or w == 0: not erased (the
+    caller has validated the table).  mode 0: zeros inside the box; mode 1: N(0,1) from Philox4x32-10 on
+    (seed, step, sample, position) — include/passl_hip.h.  ``out`` None: a new tensor (``x`` is not written);
+    ``out is x``: in place, only box elements are stored."""
+    assert x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()
+    assert boxes.dtype == torch.int32 and boxes.is_contiguous() and tuple(boxes.shape) == (x.shape[0], 4)
+    B, Cc, H, W = x.shape
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.dtype == torch.float32 and out.shape == x.shape and out.is_contiguous()
+    seed, step = int(seed) & ((1 << 64) - 1), int(step) & ((1 << 64) - 1)
+    seed -= (seed >> 63) << 64                            # the same 64-bit patterns as signed arguments
+    step -= (step >> 63) << 64
+    L.check(_lib().passl_hip_random_erase(L.ptr(x), L.ptr(out), L.ptr(boxes), B, Cc, H, W, int(mode), seed, step,
+                                          L.stream()), 'random_erase')
+    return out
+
+
 def soft_ce_fwd(scores, target):
     """scores, target fp32 [N,C] -> out[3] = (loss, acc1 %, acc5 % against argmax target), lse [N], tsum [N]."""
     assert scores.shape == target.shape and target.dtype == torch.float32
