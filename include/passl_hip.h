@@ -727,6 +727,29 @@ int passl_hip_soft_ce_bwd(const float* scores, const float* target, const float*
 int passl_hip_random_erase(const float* x, float* out, const int32_t* boxes, int B, int C, int H, int W, int mode,
                            int64_t seed, int64_t step, passl_stream_t stream);
 
+/* ---------------------------------------------------------------- random resized crop, flip, normalise
+ * Reference: RandCropImage / MAERandCropImage, RandFlipImage / RandomHorizontalFlip, NormalizeImage, ToCHWImage of
+ * passl/data/preprocess/basic_transforms.py (:373-419, :635-767), which run on the host through Pillow, sample by sample.
+ * src uint8 [B][Hs][Ws][3] (HWC, never written); out fp32 [B][3][S][S]; table: a DEVICE table int32 [B][8] =
+ * (top, left, h, w, flip, 0, 0, 0); mean_std_scale: 7 HOST floats (mean[3], std[3], scale), read during the call.
+ *   out[b] = Pillow's 8-bit Image.resize((S, S), BICUBIC) of src[b, top:top+h, left:left+w], flipped left-right when
+ *   flip != 0, then (float(v) * scale - mean[c]) / std[c], each operation rounded to fp32 on its own.
+ *   Resampling, per axis (n_in crop pixels -> S outputs), in IEEE double without contraction: scale = n_in / S,
+ *   fs = max(1, scale), support = 2 fs; output i: center = (i + 0.5) scale, lo = max((int)(center - support + 0.5), 0),
+ *   hi = min((int)(center + support + 0.5), n_in), w_k = bicubic_{a = -0.5}(((k + lo) - center + 0.5) (1 / fs)) for
+ *   k < hi - lo, divided by their sum (k order), K_k = (int)(w_k 2^22 +- 0.5) (truncation, the sign of w_k);
+ *   a pass = clip((2^21 + sum_k K_k p[lo + k]) >> 22, 0, 255).  The horizontal pass first, rounded to uint8; the vertical
+ *   pass on those values.  Taps are clamped to the crop, not to the source.  Bit-equal to the reference's PIL path.
+ * Envelope (PASSL_EUNSUPPORTED beyond): one band of 16 output rows must fit 64 KiB of LDS — with r = max(1, Hs / S),
+ * rw = max(1, Ws / S), KH = 2 ceil(2 rw) + 1, KV = 2 ceil(2 r) + 1, NR = ceil(15 r) + 2 ceil(2 r) + 3:
+ * 4 S (KH + 2) + 64 (KV + 2) + 3072 + 3 S NR (each term rounded up to 16) <= 65536.
+ * The library cannot read the table on the host: the kernel clamps every box to the source (top, left into it, then
+ * 1 <= h <= Hs - top, 1 <= w <= Ws - left), so no access leaves a tensor whatever the table holds.  NULL pointers,
+ * B < 0, Hs, Ws, S <= 0, a source or output sample of 2^31 bytes / elements or more, a zero std, out or table not
+ * 4-byte aligned -> PASSL_EINVAL; B == 0 -> PASSL_OK, nothing launched. */
+int passl_hip_crop_resize_norm(const uint8_t* src, float* out, const int32_t* table, int B, int Hs, int Ws, int S,
+                               const float* mean_std_scale, passl_stream_t stream);
+
 /* ---------------------------------------------------------------- measurement hooks */
 
 /* When enabled, every passl_hip_conv_igemm / passl_hip_conv_wgrad launch is bracketed by HIP

@@ -19,14 +19,20 @@ def build_dataloader(cfg, device):
     mixes, else None.  The Trainer hands it to every model call; only the train block's is used.
     A ``RandomErasing`` entry of ``dataset.transforms`` (preprocess.build_random_erasing) of a SyntheticLabeled source
     becomes the loader's ``batch_transform``: erasing happens in the loader, i.e. before ``mixup_fn`` — the reference's
-    order, per-sample transform first, then the collate-time mix.  Every other entry stays ignored."""
+    order, per-sample transform first, then the collate-time mix.  Every other entry stays ignored there.
+    A SyntheticRawLabeled source (uint8 HWC images) honours its whole ``transforms`` list: crop, flip, NormalizeImage and
+    ToCHWImage become one preprocess.DeviceCropPipeline, followed by the eraser when the list ends in ``RandomErasing``."""
     from .preprocess import build_mixup, build_random_erasing
-    from .synthetic import SyntheticLabeled, SyntheticLoader
+    from .preprocess.crop import ChainedBatchTransform, build_crop_pipeline
+    from .synthetic import SyntheticLabeled, SyntheticLoader, SyntheticRawLabeled
     ds_cfg = dict(cfg['dataset'])
     mixup_cfg = ds_cfg.pop('batch_transforms', None)
     sampler = cfg.get('sampler', {})
     dataset = build_dataset(ds_cfg)
     eraser = build_random_erasing(ds_cfg.get('transforms', None)) if isinstance(dataset, SyntheticLabeled) else None
+    if isinstance(dataset, SyntheticRawLabeled):
+        crop = build_crop_pipeline(ds_cfg.get('transforms', None))
+        eraser = crop if eraser is None else ChainedBatchTransform([crop, eraser])
     loader = SyntheticLoader(dataset, batch_size=sampler.get('batch_size', 32), device=device,
                              drop_last=sampler.get('drop_last', True), batch_transform=eraser)
     ring = int((cfg.get('loader', None) or {}).get('host_ring', 0) or 0)

@@ -80,6 +80,28 @@ class SyntheticLabeled(object):
 
 
 @DATASETS.register()
+class SyntheticRawLabeled(SyntheticLabeled):
+    """(image, label) pairs as a decoder hands them out: image uint8 [source_h, source_w, 3] (HWC), N(128, 48^2) rounded
+    and cut to [0, 255] plus a class-dependent colour cast (channel c shifted by 40 cos(label * (c + 1))), label int64.
+    The ``transforms`` of its config block are honoured (build_dataloader): random resized crop, flip, NormalizeImage
+    and ToCHWImage run on the resident batch in one launch (preprocess.DeviceCropPipeline), so a step receives fp32
+    [3, S, S] like SyntheticLabeled's.  A host ring moves the uint8 images: a quarter of the fp32 bytes."""
+
+    def __init__(self, num_samples=1281167, source_h=256, source_w=256, image_size=224, num_classes=1000, seed=1234,
+                 num_batches_cached=1, **ignored):
+        super().__init__(num_samples=num_samples, image_size=image_size, num_classes=num_classes, seed=seed,
+                         num_batches_cached=num_batches_cached)
+        self.source_h, self.source_w = int(source_h), int(source_w)
+
+    def make_batch(self, gen, batch_size):
+        label = torch.randint(0, self.num_classes, (batch_size,), generator=gen)
+        image = torch.randn(batch_size, self.source_h, self.source_w, 3, generator=gen) * 48. + 128.
+        shift = 40. * torch.cos(label.double().unsqueeze(1) * torch.arange(1, 4).double()).float()
+        image = (image + shift.view(batch_size, 1, 1, 3)).round().clamp(0, 255)
+        return image.to(torch.uint8), label
+
+
+@DATASETS.register()
 class ImageNet(object):
     def __init__(self, **kwargs):
         raise NotImplementedError(
@@ -122,8 +144,8 @@ class ImageFolder(object):
 
 class SyntheticLoader(object):
     """``batch_transform``: a callable applied OUT OF PLACE to the image tensor of every (image, label) batch that is
-    yielded (preprocess.RandomErasing: the per-sample transform of the reference's pipeline that can run on a resident
-    batch); the cached batch itself stays bit-unchanged.  None: batches are yielded as they are cached."""
+    yielded (preprocess.RandomErasing; for a SyntheticRawLabeled source preprocess.DeviceCropPipeline, then the eraser: the
+    per-sample transforms of the reference's pipeline, on a resident batch); the cached batch itself stays bit-unchanged.  None: batches are yielded as they are cached."""
 
     def __init__(self, dataset, batch_size, device, drop_last=True, batch_transform=None):
         self.dataset = dataset

@@ -882,6 +882,25 @@ def random_erase(x, boxes, mode, seed, step, out=None):
     return out
 
 
+# ------------------------------------------------------------------ crop + resize + flip + normalise (csrc/crop_resize.hip)
+def crop_resize_norm(src, table, size, mean, std, scale):
+    """src uint8 [B,Hs,Ws,3] (HWC, not written); table int32 [B,8] = (top, left, h, w, flip, 0, 0, 0) on the device (the
+    caller has validated it) -> a new fp32 [B,3,size,size]: Pillow's 8-bit bicubic resize of every crop, flipped
+    left-right where flip is set, then (float(v) * scale - mean[c]) / std[c] — include/passl_hip.h.  mean, std: three
+    Python floats each, scale: one; they are rounded to fp32 here."""
+    assert src.dtype == torch.uint8 and src.dim() == 4 and src.shape[3] == 3 and src.is_contiguous()
+    assert table.dtype == torch.int32 and table.is_contiguous() and tuple(table.shape) == (src.shape[0], 8)
+    B, Hs, Ws, _ = src.shape
+    size = int(size)
+    out = torch.empty(B, 3, size, size, dtype=torch.float32, device=src.device)
+    if B == 0 and src.is_cuda:
+        return out                                        # (an empty tensor has no address to hand over)
+    consts = (C.c_float * 7)(*[float(v) for v in mean], *[float(v) for v in std], float(scale))
+    L.check(_lib().passl_hip_crop_resize_norm(L.ptr(src), L.ptr(out), L.ptr(table), B, Hs, Ws, size,
+                                              C.cast(consts, C.c_void_p), L.stream()), 'crop_resize_norm')
+    return out
+
+
 def soft_ce_fwd(scores, target):
     """scores, target fp32 [N,C] -> out[3] = (loss, acc1 %, acc5 % against argmax target), lse [N], tsum [N]."""
     assert scores.shape == target.shape and target.dtype == torch.float32
