@@ -539,30 +539,43 @@ __device__ __forceinline__ void adamw_update(float* __restrict__ pp, const float
   }
 }
 
-__global__ void __launch_bounds__(kThreads) adamw_kernel(float* __restrict__ p,
-                                                         const float* __restrict__ g,
-                                                         float* __restrict__ m, float* __restrict__ v,
-                                                         int64_t n, float lr, float b1p, float b2p,
-                                                         const float* __restrict__ hyper, float wd, float eps,
-                                                         float b1, float b2, float gs) {
+// One float4 of each buffer through adamw_update: the body of both walks below.
+template <bool kClip>
+__device__ __forceinline__ void adamw_update4(float* __restrict__ p, const float* __restrict__ g,
+                                              float* __restrict__ m, float* __restrict__ v, int64_t i, float lr,
+                                              float wd, float b1p, float b2p, float eps, float b1, float b2, float gs,
+                                              float coef) {
+  float4 pv = reinterpret_cast<float4*>(p)[i];
+  const float4 gv = reinterpret_cast<const float4*>(g)[i];
+  float4 mv = reinterpret_cast<float4*>(m)[i];
+  float4 vv = reinterpret_cast<float4*>(v)[i];
+  adamw_update<kClip>(&pv.x, &gv.x, &mv.x, &vv.x, 4, lr, wd, b1p, b2p, eps, b1, b2, gs, coef);
+  reinterpret_cast<float4*>(p)[i] = pv;
+  reinterpret_cast<float4*>(m)[i] = mv;
+  reinterpret_cast<float4*>(v)[i] = vv;
+}
+
+// The flat grid-stride walk.  kClip: the gradient times ONE coefficient that grad_clip_finalize_kernel (flat.hip) left
+// in device memory at coef_p.  Only the unclipped instantiation takes the step-dependent scalars by value
+// (hyper == nullptr) and an n that is no multiple of 4: the clipped one is reached with hyper and n % 4 == 0 only.
+template <bool kClip>
+__global__ void __launch_bounds__(kThreads) adamw_flat_kernel(
+    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
+    float lr, float b1p, float b2p, const float* __restrict__ hyper, float wd, float eps, float b1, float b2, float gs,
+    const float* __restrict__ coef_p) {
   // the step-dependent scalars come by value or from device memory (hyper = {lr, beta1^t, beta2^t}: HIP-graph
   // replays); the derived ones are computed here either way
-  if (hyper) { lr = hyper[0]; b1p = hyper[1]; b2p = hyper[2]; }
+  if (kClip || hyper) { lr = hyper[0]; b1p = hyper[1]; b2p = hyper[2]; }
+  const float coef = kClip ? coef_p[0] : 1.f;
   const int64_t nv = n >> 2;
   const int64_t stride = (int64_t)gridDim.x * kThreads;
-  for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < nv; i += stride) {
-    float4 pv = reinterpret_cast<float4*>(p)[i];
-    const float4 gv = reinterpret_cast<const float4*>(g)[i];
-    float4 mv = reinterpret_cast<float4*>(m)[i];
-    float4 vv = reinterpret_cast<float4*>(v)[i];
-    adamw_update(&pv.x, &gv.x, &mv.x, &vv.x, 4, lr, wd, b1p, b2p, eps, b1, b2, gs);
-    reinterpret_cast<float4*>(p)[i] = pv;
-    reinterpret_cast<float4*>(m)[i] = mv;
-    reinterpret_cast<float4*>(v)[i] = vv;
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-    const int64_t i = (nv << 2) + threadIdx.x;
-    adamw_update(p + i, g + i, m + i, v + i, 1, lr, wd, b1p, b2p, eps, b1, b2, gs);
+  for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < nv; i += stride)
+    adamw_update4<kClip>(p, g, m, v, i, lr, wd, b1p, b2p, eps, b1, b2, gs, coef);
+  if constexpr (!kClip) {
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+      const int64_t i = (nv << 2) + threadIdx.x;
+      adamw_update(p + i, g + i, m + i, v + i, 1, lr, wd, b1p, b2p, eps, b1, b2, gs);
+    }
   }
 }
 
@@ -573,10 +586,14 @@ __global__ void __launch_bounds__(kThreads) adamw_kernel(float* __restrict__ p,
 // the block's previous tile (offsets ascend); a lane then steps forward while its own float4 lies beyond that segment
 // — no step at all unless a boundary falls inside the tile.  The table stays in global memory: no segment limit.
 // The cursor never leaves [0, n_seg) and the data accesses are bounded by n whatever the table holds.
-__global__ void __launch_bounds__(kThreads) adamw_groups_kernel(
+// kClip: clip = the {norm, coef} table of grad_clip_finalize_kernel, seg_set[s] the set of segment s (outside
+// [0, n_sets): coefficient 1 — a parameter excluded from clipping).
+template <bool kClip>
+__global__ void __launch_bounds__(kThreads) adamw_segments_kernel(
     float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
     const int64_t* __restrict__ seg_end, const float* __restrict__ seg_lr_scale, const float* __restrict__ seg_wd,
-    int n_seg, const float* __restrict__ hyper, float eps, float b1, float b2, float gs) {
+    int n_seg, const float* __restrict__ hyper, float eps, float b1, float b2, float gs,
+    const int32_t* __restrict__ seg_set, const float* __restrict__ clip, int n_sets) {
   const float lr = hyper[0], b1p = hyper[1], b2p = hyper[2];
   const int64_t nv = n >> 2;
   const int64_t stride = (int64_t)gridDim.x * kThreads;
@@ -594,73 +611,12 @@ __global__ void __launch_bounds__(kThreads) adamw_groups_kernel(
     while (s + 1 < n_seg && (i << 2) >= seg_end[s]) ++s;
     const float lr_s = lr * seg_lr_scale[s];
     const float wd_s = seg_wd[s];
-    float4 pv = reinterpret_cast<float4*>(p)[i];
-    const float4 gv = reinterpret_cast<const float4*>(g)[i];
-    float4 mv = reinterpret_cast<float4*>(m)[i];
-    float4 vv = reinterpret_cast<float4*>(v)[i];
-    adamw_update(&pv.x, &gv.x, &mv.x, &vv.x, 4, lr_s, wd_s, b1p, b2p, eps, b1, b2, gs);
-    reinterpret_cast<float4*>(p)[i] = pv;
-    reinterpret_cast<float4*>(m)[i] = mv;
-    reinterpret_cast<float4*>(v)[i] = vv;
-  }
-}
-
-// The clip variants: the same walks, the gradient times a coefficient that grad_clip_finalize_kernel (flat.hip) left in
-// device memory.  Flat: one coefficient.  Grouped: clip = the {norm, coef} table, seg_set[s] the set of segment s
-// (outside [0, n_sets): coefficient 1 — a parameter excluded from clipping).  n % 4 == 0 for both.
-__global__ void __launch_bounds__(kThreads) adamw_clip_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                              float* __restrict__ m, float* __restrict__ v, int64_t n,
-                                                              const float* __restrict__ hyper,
-                                                              const float* __restrict__ coef_p, float wd, float eps,
-                                                              float b1, float b2, float gs) {
-  const float lr = hyper[0], b1p = hyper[1], b2p = hyper[2];
-  const float coef = coef_p[0];
-  const int64_t nv = n >> 2;
-  const int64_t stride = (int64_t)gridDim.x * kThreads;
-  for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < nv; i += stride) {
-    float4 pv = reinterpret_cast<float4*>(p)[i];
-    const float4 gv = reinterpret_cast<const float4*>(g)[i];
-    float4 mv = reinterpret_cast<float4*>(m)[i];
-    float4 vv = reinterpret_cast<float4*>(v)[i];
-    adamw_update<true>(&pv.x, &gv.x, &mv.x, &vv.x, 4, lr, wd, b1p, b2p, eps, b1, b2, gs, coef);
-    reinterpret_cast<float4*>(p)[i] = pv;
-    reinterpret_cast<float4*>(m)[i] = mv;
-    reinterpret_cast<float4*>(v)[i] = vv;
-  }
-}
-
-__global__ void __launch_bounds__(kThreads) adamw_groups_clip_kernel(
-    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int64_t n,
-    const int64_t* __restrict__ seg_end, const float* __restrict__ seg_lr_scale, const float* __restrict__ seg_wd,
-    const int32_t* __restrict__ seg_set, int n_seg, const float* __restrict__ hyper, const float* __restrict__ clip,
-    int n_sets, float eps, float b1, float b2, float gs) {
-  const float lr = hyper[0], b1p = hyper[1], b2p = hyper[2];
-  const int64_t nv = n >> 2;
-  const int64_t stride = (int64_t)gridDim.x * kThreads;
-  int s0 = 0;
-  for (int64_t tile = (int64_t)blockIdx.x * kThreads; tile < nv; tile += stride) {
-    const int64_t first = tile << 2;
-    int hi = n_seg - 1;
-    while (s0 < hi) {
-      const int mid = (s0 + hi) >> 1;
-      if (first < seg_end[mid]) hi = mid; else s0 = mid + 1;
+    float coef = 1.f;
+    if constexpr (kClip) {
+      const int set = seg_set[s];
+      if (set >= 0 && set < n_sets) coef = clip[2 * set + 1];
     }
-    const int64_t i = tile + threadIdx.x;
-    if (i >= nv) continue;
-    int s = s0;
-    while (s + 1 < n_seg && (i << 2) >= seg_end[s]) ++s;
-    const float lr_s = lr * seg_lr_scale[s];
-    const float wd_s = seg_wd[s];
-    const int set = seg_set[s];
-    const float coef = (set >= 0 && set < n_sets) ? clip[2 * set + 1] : 1.f;
-    float4 pv = reinterpret_cast<float4*>(p)[i];
-    const float4 gv = reinterpret_cast<const float4*>(g)[i];
-    float4 mv = reinterpret_cast<float4*>(m)[i];
-    float4 vv = reinterpret_cast<float4*>(v)[i];
-    adamw_update<true>(&pv.x, &gv.x, &mv.x, &vv.x, 4, lr_s, wd_s, b1p, b2p, eps, b1, b2, gs, coef);
-    reinterpret_cast<float4*>(p)[i] = pv;
-    reinterpret_cast<float4*>(m)[i] = mv;
-    reinterpret_cast<float4*>(v)[i] = vv;
+    adamw_update4<kClip>(p, g, m, v, i, lr_s, wd_s, b1p, b2p, eps, b1, b2, gs, coef);
   }
 }
 
@@ -911,17 +867,26 @@ extern "C" int passl_hip_mae_loss_bwd(const float* img, const float* pred, const
   return PASSL_OK;
 }
 
-static int adamw_impl(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1_pow,
-                      float beta2_pow, const float* hyper, float beta1, float beta2, float epsilon,
-                      float weight_decay, float grad_scale, passl_stream_t stream) {
-  if (!p || !g || !m || !v || n < 0 || !aligned16(p) || !aligned16(g) || !aligned16(m) || !aligned16(v))
-    return PASSL_EINVAL;
-  if (n == 0) return PASSL_OK;
+// What the five AdamW entry points ask of their common arguments, and their grid: one thread per float4, capped — the
+// walks are grid-stride.
+static inline bool adamw_buffers_ok(const float* p, const float* g, const float* m, const float* v, int64_t n) {
+  return p && g && m && v && n >= 0 && aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v);
+}
+static inline unsigned adamw_grid(int64_t n) {
   int64_t b = ((n >> 2) + kThreads - 1) / kThreads;
   if (b > 2048) b = 2048;
   if (b < 1) b = 1;
-  hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)b), dim3(kThreads), 0, as_stream(stream), p, g, m, v, n,
-                     lr, beta1_pow, beta2_pow, hyper, weight_decay, epsilon, beta1, beta2, grad_scale);
+  return (unsigned)b;
+}
+
+template <bool kClip>
+static int adamw_flat(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1_pow,
+                      float beta2_pow, const float* hyper, const float* coef, float beta1, float beta2, float epsilon,
+                      float weight_decay, float grad_scale, passl_stream_t stream) {
+  if (!adamw_buffers_ok(p, g, m, v, n)) return PASSL_EINVAL;
+  if (n == 0) return PASSL_OK;
+  hipLaunchKernelGGL(adamw_flat_kernel<kClip>, dim3(adamw_grid(n)), dim3(kThreads), 0, as_stream(stream), p, g, m, v,
+                     n, lr, beta1_pow, beta2_pow, hyper, weight_decay, epsilon, beta1, beta2, grad_scale, coef);
   PASSL_RETURN_IF_LAUNCH_FAILED();
   return PASSL_OK;
 }
@@ -930,49 +895,51 @@ extern "C" int passl_hip_adamw(float* p, const float* g, float* m, float* v, int
                                float beta1, float beta2, float epsilon, float weight_decay,
                                float beta1_pow, float beta2_pow, float grad_scale,
                                passl_stream_t stream) {
-  return adamw_impl(p, g, m, v, n, lr, beta1_pow, beta2_pow, nullptr, beta1, beta2, epsilon, weight_decay,
-                    grad_scale, stream);
+  return adamw_flat<false>(p, g, m, v, n, lr, beta1_pow, beta2_pow, nullptr, nullptr, beta1, beta2, epsilon,
+                           weight_decay, grad_scale, stream);
 }
 
 extern "C" int passl_hip_adamw_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper,
                                    float beta1, float beta2, float epsilon, float weight_decay, float grad_scale,
                                    passl_stream_t stream) {
   if (!hyper) return PASSL_EINVAL;
-  return adamw_impl(p, g, m, v, n, 0.f, 0.f, 0.f, hyper, beta1, beta2, epsilon, weight_decay, grad_scale, stream);
+  return adamw_flat<false>(p, g, m, v, n, 0.f, 0.f, 0.f, hyper, nullptr, beta1, beta2, epsilon, weight_decay,
+                           grad_scale, stream);
+}
+
+extern "C" int passl_hip_adamw_clip_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper,
+                                        const float* coef, float beta1, float beta2, float epsilon,
+                                        float weight_decay, float grad_scale, passl_stream_t stream) {
+  if (!hyper || !coef || (n & 3) || (reinterpret_cast<uintptr_t>(hyper) & 3u) ||
+      (reinterpret_cast<uintptr_t>(coef) & 3u))
+    return PASSL_EINVAL;
+  return adamw_flat<true>(p, g, m, v, n, 0.f, 0.f, 0.f, hyper, coef, beta1, beta2, epsilon, weight_decay, grad_scale,
+                          stream);
+}
+
+template <bool kClip>
+static int adamw_segments(float* p, const float* g, float* m, float* v, int64_t n, const int64_t* seg_end,
+                          const float* seg_lr_scale, const float* seg_wd, const int32_t* seg_set, int n_seg,
+                          const float* hyper, const float* clip, int n_sets, float beta1, float beta2, float epsilon,
+                          float grad_scale, passl_stream_t stream) {
+  if (!adamw_buffers_ok(p, g, m, v, n) || !hyper || !seg_end || !seg_lr_scale || !seg_wd || (n & 3) || n_seg <= 0 ||
+      (reinterpret_cast<uintptr_t>(seg_end) & 7u) || (reinterpret_cast<uintptr_t>(seg_lr_scale) & 3u) ||
+      (reinterpret_cast<uintptr_t>(seg_wd) & 3u) || (reinterpret_cast<uintptr_t>(hyper) & 3u))
+    return PASSL_EINVAL;
+  if (n == 0) return PASSL_OK;
+  hipLaunchKernelGGL(adamw_segments_kernel<kClip>, dim3(adamw_grid(n)), dim3(kThreads), 0, as_stream(stream), p, g, m,
+                     v, n, seg_end, seg_lr_scale, seg_wd, n_seg, hyper, epsilon, beta1, beta2, grad_scale, seg_set,
+                     clip, n_sets);
+  PASSL_RETURN_IF_LAUNCH_FAILED();
+  return PASSL_OK;
 }
 
 extern "C" int passl_hip_adamw_groups_dev(float* p, const float* g, float* m, float* v, int64_t n,
                                           const int64_t* seg_end, const float* seg_lr_scale, const float* seg_wd,
                                           int n_seg, const float* hyper, float beta1, float beta2, float epsilon,
                                           float grad_scale, passl_stream_t stream) {
-  if (!p || !g || !m || !v || !hyper || !seg_end || !seg_lr_scale || !seg_wd || n < 0 || (n & 3) || n_seg <= 0 ||
-      !aligned16(p) || !aligned16(g) || !aligned16(m) || !aligned16(v) ||
-      (reinterpret_cast<uintptr_t>(seg_end) & 7u) || (reinterpret_cast<uintptr_t>(seg_lr_scale) & 3u) ||
-      (reinterpret_cast<uintptr_t>(seg_wd) & 3u) || (reinterpret_cast<uintptr_t>(hyper) & 3u))
-    return PASSL_EINVAL;
-  if (n == 0) return PASSL_OK;
-  int64_t b = ((n >> 2) + kThreads - 1) / kThreads;       // the flat kernel's grid
-  if (b > 2048) b = 2048;
-  hipLaunchKernelGGL(adamw_groups_kernel, dim3((unsigned)b), dim3(kThreads), 0, as_stream(stream), p, g, m, v, n,
-                     seg_end, seg_lr_scale, seg_wd, n_seg, hyper, epsilon, beta1, beta2, grad_scale);
-  PASSL_RETURN_IF_LAUNCH_FAILED();
-  return PASSL_OK;
-}
-
-extern "C" int passl_hip_adamw_clip_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper,
-                                        const float* coef, float beta1, float beta2, float epsilon,
-                                        float weight_decay, float grad_scale, passl_stream_t stream) {
-  if (!p || !g || !m || !v || !hyper || !coef || n < 0 || (n & 3) || !aligned16(p) || !aligned16(g) ||
-      !aligned16(m) || !aligned16(v) || (reinterpret_cast<uintptr_t>(hyper) & 3u) ||
-      (reinterpret_cast<uintptr_t>(coef) & 3u))
-    return PASSL_EINVAL;
-  if (n == 0) return PASSL_OK;
-  int64_t b = ((n >> 2) + kThreads - 1) / kThreads;       // the flat kernel's grid
-  if (b > 2048) b = 2048;
-  hipLaunchKernelGGL(adamw_clip_kernel, dim3((unsigned)b), dim3(kThreads), 0, as_stream(stream), p, g, m, v, n,
-                     hyper, coef, weight_decay, epsilon, beta1, beta2, grad_scale);
-  PASSL_RETURN_IF_LAUNCH_FAILED();
-  return PASSL_OK;
+  return adamw_segments<false>(p, g, m, v, n, seg_end, seg_lr_scale, seg_wd, nullptr, n_seg, hyper, nullptr, 0, beta1,
+                               beta2, epsilon, grad_scale, stream);
 }
 
 extern "C" int passl_hip_adamw_groups_clip_dev(float* p, const float* g, float* m, float* v, int64_t n,
@@ -980,18 +947,9 @@ extern "C" int passl_hip_adamw_groups_clip_dev(float* p, const float* g, float* 
                                                const float* seg_wd, const int32_t* seg_set, int n_seg,
                                                const float* hyper, const float* clip, int n_sets, float beta1,
                                                float beta2, float epsilon, float grad_scale, passl_stream_t stream) {
-  if (!p || !g || !m || !v || !hyper || !clip || !seg_end || !seg_lr_scale || !seg_wd || !seg_set || n < 0 ||
-      (n & 3) || n_seg <= 0 || n_sets <= 0 || !aligned16(p) || !aligned16(g) || !aligned16(m) || !aligned16(v) ||
-      (reinterpret_cast<uintptr_t>(seg_end) & 7u) || (reinterpret_cast<uintptr_t>(seg_lr_scale) & 3u) ||
-      (reinterpret_cast<uintptr_t>(seg_wd) & 3u) || (reinterpret_cast<uintptr_t>(seg_set) & 3u) ||
-      (reinterpret_cast<uintptr_t>(hyper) & 3u) || (reinterpret_cast<uintptr_t>(clip) & 3u))
+  if (!clip || !seg_set || n_sets <= 0 || (reinterpret_cast<uintptr_t>(seg_set) & 3u) ||
+      (reinterpret_cast<uintptr_t>(clip) & 3u))
     return PASSL_EINVAL;
-  if (n == 0) return PASSL_OK;
-  int64_t b = ((n >> 2) + kThreads - 1) / kThreads;
-  if (b > 2048) b = 2048;
-  hipLaunchKernelGGL(adamw_groups_clip_kernel, dim3((unsigned)b), dim3(kThreads), 0, as_stream(stream), p, g, m, v, n,
-                     seg_end, seg_lr_scale, seg_wd, seg_set, n_seg, hyper, clip, n_sets, epsilon, beta1, beta2,
-                     grad_scale);
-  PASSL_RETURN_IF_LAUNCH_FAILED();
-  return PASSL_OK;
+  return adamw_segments<true>(p, g, m, v, n, seg_end, seg_lr_scale, seg_wd, seg_set, n_seg, hyper, clip, n_sets, beta1,
+                              beta2, epsilon, grad_scale, stream);
 }

@@ -99,38 +99,33 @@ class _DeviceHyper(object):
         return self._hyper_dev
 
 
-@OPTIMIZERS.register()
-class Momentum(_DeviceHyper):
-    type = 'momentum'
+class _ArenaOptimizer(_DeviceHyper):
+    """An optimizer over flat arenas: every listed trainable parameter lives in an EncoderArena, every parameter of
+    such an arena is listed exactly once, and the state is a few flat vectors per arena (``_STATE``), saved and
+    loaded under the keys ``<name>_<arena index>``.  A subclass adds its rule (``step``) and its configuration."""
 
-    def __init__(self, learning_rate=0.001, momentum=0.9, parameters=None, use_nesterov=False,
-                 weight_decay=None, grad_clip=None, multi_precision=False, rescale_grad=1.0,
-                 name=None, use_master_param=None, lr_func=None):
-        # v2 spelling (passl/optimizer/momentum.py:25-45): use_master_param asks for fp32 masters next to fp16
-        # parameters — the arena's parameters ARE fp32 masters; lr_func (LRCallable groups) is not used by the recipes
-        if use_nesterov:
-            raise NotImplementedError('nesterov momentum is not used on the MoCo path')
-        if grad_clip is not None or lr_func is not None:
-            raise NotImplementedError('grad_clip / lr_func are not used on the MoCo path')
-        self._learning_rate = learning_rate
-        self._momentum = float(momentum)
-        self._wd = float(weight_decay) if weight_decay else 0.0
-        self._rescale = float(rescale_grad)
-        self._parameter_list = [p for p in (parameters or []) if p.requires_grad]
-        arenas = []
-        for p in self._parameter_list:
+    _STATE = ()        # ((state_dict key prefix, attribute: one flat vector per arena), ...)
+
+    def _init_arenas(self, parameters):
+        params = [p for p in (parameters or []) if p.requires_grad]
+        arenas, seen = [], set()
+        for p in params:
             a = getattr(p, '_passl_arena', None)
             if a is None:
-                raise NotImplementedError('Momentum optimises parameters that live in an '
-                                          'EncoderArena (flat buffer); got a free tensor')
+                raise NotImplementedError('%s optimises parameters that live in an EncoderArena (flat buffer); '
+                                          'got a free tensor' % type(self).__name__)
+            if id(p) in seen:
+                raise ValueError('a parameter appears more than once in the parameter list / groups')
+            seen.add(id(p))
             if a not in arenas:
                 arenas.append(a)
         for a in arenas:
-            n_listed = sum(1 for p in self._parameter_list if p._passl_arena is a)
-            if n_listed != len(a.param_slices):
+            if sum(1 for p in params if p._passl_arena is a) != len(a.param_slices):
                 raise NotImplementedError('optimising a subset of an arena is not supported')
+        self._parameter_list = params
         self._arenas = arenas
-        self._velocity = [torch.zeros_like(a.flat[:a.n_train]) for a in arenas]
+        for _key, attr in self._STATE:
+            setattr(self, attr, [torch.zeros_like(a.flat[:a.n_train]) for a in arenas])
         self.grad_scale = 1.0      # set by the DP reducer to 1/world_size (sum -> mean)
         self._init_hyper(arenas[0].device if arenas else torch.device('cpu'))
 
@@ -145,6 +140,41 @@ class Momentum(_DeviceHyper):
 
     clear_gradients = clear_grad
 
+    def state_dict(self):
+        sd = {'%s_%d' % (key, i): x.detach().cpu()
+              for key, attr in self._STATE for i, x in enumerate(getattr(self, attr))}
+        if isinstance(self._learning_rate, LRScheduler):
+            sd['LR_Scheduler'] = self._learning_rate.state_dict()
+        return sd
+
+    def set_state_dict(self, sd):
+        for key, attr in self._STATE:
+            for i, x in enumerate(getattr(self, attr)):
+                _load_flat_state(x, sd, '%s_%d' % (key, i))
+        if 'LR_Scheduler' in sd and isinstance(self._learning_rate, LRScheduler):
+            self._learning_rate.set_state_dict(sd['LR_Scheduler'])
+
+
+@OPTIMIZERS.register()
+class Momentum(_ArenaOptimizer):
+    type = 'momentum'
+    _STATE = (('velocity', '_velocity'),)
+
+    def __init__(self, learning_rate=0.001, momentum=0.9, parameters=None, use_nesterov=False,
+                 weight_decay=None, grad_clip=None, multi_precision=False, rescale_grad=1.0,
+                 name=None, use_master_param=None, lr_func=None):
+        # v2 spelling (passl/optimizer/momentum.py:25-45): use_master_param asks for fp32 masters next to fp16
+        # parameters — the arena's parameters ARE fp32 masters; lr_func (LRCallable groups) is not used by the recipes
+        if use_nesterov:
+            raise NotImplementedError('nesterov momentum is not used on the MoCo path')
+        if grad_clip is not None or lr_func is not None:
+            raise NotImplementedError('grad_clip / lr_func are not used on the MoCo path')
+        self._learning_rate = learning_rate
+        self._momentum = float(momentum)
+        self._wd = float(weight_decay) if weight_decay else 0.0
+        self._rescale = float(rescale_grad)
+        self._init_arenas(parameters)
+
     @torch.no_grad()
     def step(self):
         hyper = self._hyper_for_step()
@@ -152,18 +182,6 @@ class Momentum(_DeviceHyper):
             _grads_complete(a)
             ops.momentum_sgd_dev(a.flat[:a.n_train], a.grads, v, hyper, self._momentum, self._wd,
                                  self.grad_scale * self._rescale)
-
-    def state_dict(self):
-        sd = {'velocity_%d' % i: v.detach().cpu() for i, v in enumerate(self._velocity)}
-        if isinstance(self._learning_rate, LRScheduler):
-            sd['LR_Scheduler'] = self._learning_rate.state_dict()
-        return sd
-
-    def set_state_dict(self, sd):
-        for i, v in enumerate(self._velocity):
-            _load_flat_state(v, sd, 'velocity_%d' % i)
-        if 'LR_Scheduler' in sd and isinstance(self._learning_rate, LRScheduler):
-            self._learning_rate.set_state_dict(sd['LR_Scheduler'])
 
 
 def _paddle_auto_names(arena):
@@ -222,7 +240,7 @@ def paddle_param_names(model):
 
 
 @OPTIMIZERS.register()
-class LarsMomentumOptimizer(_DeviceHyper):
+class LarsMomentumOptimizer(_ArenaOptimizer):
     """paddle.fluid.optimizer.LarsMomentumOptimizer (registered by the reference at
     passl_v110/solver/optimizer.py:25, built with ``parameter_list=`` at solver/builder.py:198-201,
     driven through ``minimize(loss)`` / ``clear_gradients()`` by hooks/optimizer_hook.py:26-45)
@@ -235,6 +253,7 @@ class LarsMomentumOptimizer(_DeviceHyper):
     ``exclude_from_weight_decay``: wd = 0 for parameters whose *Paddle name* contains one of the
     strings — the yaml's ["scale","offset",".bias"] match none of the dygraph auto-names."""
     type = 'lars_momentum'
+    _STATE = (('velocity', '_velocity'),)
 
     def __init__(self, learning_rate, momentum, lars_coeff=0.001, lars_weight_decay=0.0005,
                  parameter_list=None, regularization=None, grad_clip=None, name=None,
@@ -249,24 +268,8 @@ class LarsMomentumOptimizer(_DeviceHyper):
         self._eps = float(epsilon)
         self._rescale = float(rescale_grad)
         self._exclude = list(exclude_from_weight_decay or [])
-        params = [p for p in (parameter_list or []) if p.requires_grad]
-        arenas = []
-        for p in params:
-            a = getattr(p, '_passl_arena', None)
-            if a is None:
-                raise NotImplementedError('LarsMomentumOptimizer optimises parameters that live in '
-                                          'an EncoderArena (flat buffer); got a free tensor')
-            if a not in arenas:
-                arenas.append(a)
-        for a in arenas:
-            if sum(1 for p in params if p._passl_arena is a) != len(a.param_slices):
-                raise NotImplementedError('optimising a subset of an arena is not supported')
-        self._parameter_list = params
-        self._arenas = arenas
-        self._velocity = [torch.zeros_like(a.flat[:a.n_train]) for a in arenas]
-        self._tables = [self._build_table(a) for a in arenas]
-        self.grad_scale = 1.0
-        self._init_hyper(arenas[0].device if arenas else torch.device('cpu'))
+        self._init_arenas(parameter_list)
+        self._tables = [self._build_table(a) for a in self._arenas]
 
     def _build_table(self, arena, chunk=4096):
         names = _paddle_auto_names(arena)
@@ -286,16 +289,6 @@ class LarsMomentumOptimizer(_DeviceHyper):
                     seg_wd=torch.tensor(seg_wd, dtype=torch.float32, device=dev),
                     norms=torch.zeros(len(seg_wd) + len(blk_len), 2, dtype=torch.float32, device=dev))
 
-    def get_lr(self):
-        lr = self._learning_rate
-        return float(lr()) if isinstance(lr, LRScheduler) else float(lr)
-
-    def clear_gradients(self, set_to_zero=True):
-        for a in self._arenas:
-            a.clear_grad()
-
-    clear_grad = clear_gradients
-
     @torch.no_grad()
     def step(self):
         hyper = self._hyper_for_step()
@@ -307,18 +300,6 @@ class LarsMomentumOptimizer(_DeviceHyper):
     def minimize(self, loss=None, startup_program=None, parameters=None, no_grad_set=None):
         """Dygraph ``minimize``: the gradients already exist (the hook called backward())."""
         self.step()
-
-    def state_dict(self):
-        sd = {'velocity_%d' % i: v.detach().cpu() for i, v in enumerate(self._velocity)}
-        if isinstance(self._learning_rate, LRScheduler):
-            sd['LR_Scheduler'] = self._learning_rate.state_dict()
-        return sd
-
-    def set_state_dict(self, sd):
-        for i, v in enumerate(self._velocity):
-            _load_flat_state(v, sd, 'velocity_%d' % i)
-        if 'LR_Scheduler' in sd and isinstance(self._learning_rate, LRScheduler):
-            self._learning_rate.set_state_dict(sd['LR_Scheduler'])
 
 
 @OPTIMIZERS.register()
@@ -350,8 +331,95 @@ class MomentumLARC(LarsMomentumOptimizer):
                                   self._eps, self._clip, self.grad_scale * self._rescale)
 
 
+_GROUP_KEYS = ('params', 'weight_decay', 'learning_rate', 'lr_scale')
+
+
+def _listed_parameters(parameters, default_wd):
+    """A plain list or a list of group dicts -> [(parameter, multiplier, decay, group)] of the trainable ones (a plain
+    list is group 0 with multiplier 1 and the optimizer's decay)."""
+    parameters = list(parameters or [])
+    if not any(isinstance(g, dict) for g in parameters):
+        return [(p, 1.0, default_wd, 0) for p in parameters if p.requires_grad]
+    if not all(isinstance(g, dict) for g in parameters):
+        raise ValueError('parameters: a list of tensors or a list of group dicts, not a mixture')
+    listed = []
+    for gi, group in enumerate(parameters):
+        unknown = [k for k in group if k not in _GROUP_KEYS]
+        if unknown or 'params' not in group:
+            raise ValueError('parameter group %d: keys %r (known: %r, params required)'
+                             % (gi, sorted(group), _GROUP_KEYS))
+        if 'learning_rate' in group and 'lr_scale' in group:
+            raise ValueError('parameter group %d gives its multiplier twice (learning_rate and lr_scale)' % gi)
+        scale = float(group.get('learning_rate', group.get('lr_scale', 1.0)))
+        wd = group.get('weight_decay', None)
+        wd = default_wd if wd is None else float(wd)
+        if wd < 0:
+            raise ValueError('parameter group %d: weight_decay must be >= 0, got %r' % (gi, wd))
+        listed += [(p, scale, wd, gi) for p in group['params'] if p.requires_grad]
+    return listed
+
+
+def _arena_rows(names, listed, lr_ratio, apply_decay_param_fun, grad_clip):
+    """One arena: its Paddle auto-names and its entries of ``listed`` -> (rows, sets) in arena order.  rows[i] = (name,
+    multiplier, decay) after ``lr_ratio`` / ``apply_decay_param_fun``; sets[i] = the clip set of the parameter (its
+    group under the 'group' scope, 0 under 'global'), -1 when it is left out of clipping or nothing is clipped."""
+    rows, sets = [None] * len(names), [-1] * len(names)
+    for p, scale, wd, gi in listed:
+        name = names[p._passl_index]
+        if grad_clip is not None and not grad_clip.excludes(p, name):
+            sets[p._passl_index] = 0 if grad_clip.scope == 'global' else gi
+        if lr_ratio is not None:
+            scale = scale * float(lr_ratio(p))
+        if apply_decay_param_fun is not None and not apply_decay_param_fun(name):
+            wd = 0.0
+        rows[p._passl_index] = (name, scale, wd)
+    return rows, sets
+
+
+def _slot_ends(param_slices, n_train):
+    """Exclusive end of every parameter's slot: slot padding goes with the parameter in front of it."""
+    return [off for off, _n in param_slices[1:]] + [n_train]
+
+
+def _clip_runs(param_slices, n_train, sets):
+    """-> [(start, end, set)]: the clipped slots of one arena, adjacent slots of equal set merged (the chunk table of
+    ops.grad_clip_plan)."""
+    runs = []
+    for (start, _n), end, st in zip(param_slices, _slot_ends(param_slices, n_train), sets):
+        if st < 0:
+            continue
+        if runs and runs[-1][1] == start and runs[-1][2] == st:
+            runs[-1] = (runs[-1][0], end, st)
+        else:
+            runs.append((start, end, st))
+    return runs
+
+
+def _flat_or_segments(param_slices, n_train, rows, sets):
+    """The launch of one arena.  ``sets``: None without a clip plan.  -> (flat, segments), one of them None:
+    flat = (decay, set or None) when every multiplier is exactly 1.0 and all decays and sets are equal — the flat
+    kernel, launch for launch what a plain list gets; segments = (seg_end, seg_scale, seg_wd, seg_set or None), adjacent
+    parameters of equal (multiplier, decay, set) merged.  An arena none of whose parameters is clipped has no sets: it
+    takes the unclipped launch."""
+    if sets is not None and all(st < 0 for st in sets):
+        sets = None
+    if all(s == 1.0 for _n, s, _w in rows) and len({w for _n, _s, w in rows}) == 1 \
+            and (sets is None or len(set(sets)) == 1):
+        return (rows[0][2], None if sets is None else sets[0]), None
+    seg_end, seg_scale, seg_wd, seg_set = [], [], [], []
+    for end, (_name, scale, wd), st in zip(_slot_ends(param_slices, n_train), rows, sets or [None] * len(rows)):
+        if seg_end and (seg_scale[-1], seg_wd[-1], seg_set[-1]) == (scale, wd, st):
+            seg_end[-1] = end
+        else:
+            seg_end.append(end)
+            seg_scale.append(scale)
+            seg_wd.append(wd)
+            seg_set.append(st)
+    return None, (seg_end, seg_scale, seg_wd, None if sets is None else seg_set)
+
+
 @OPTIMIZERS.register()
-class AdamW(_DeviceHyper):
+class AdamW(_ArenaOptimizer):
     """paddle.optimizer.AdamW (registered by the reference at passl_v110/solver/optimizer.py:22) as ONE
     launch over the flat arena.  adamw op  [Paddle-semantics]:
         p *= 1 - lr*wd;  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;
@@ -368,10 +436,15 @@ class AdamW(_DeviceHyper):
     per arena (arena order, adjacent parameters with equal (multiplier, decay) merged; slot padding goes with the
     parameter in front of it) for the grouped kernel (ops.adamw_groups_dev).  Multipliers all exactly 1.0 and decays
     all equal = the flat kernel, launch for launch what a plain list gets.  The table is configuration, not state:
-    state_dict() holds the flat moments only."""
-    type = 'adamw'
+    state_dict() holds the flat moments only.
 
-    _GROUP_KEYS = ('params', 'weight_decay', 'learning_rate', 'lr_scale')
+    ``grad_clip`` (core.grad_clip.ClipGradByGlobalNorm): the clip set of a parameter joins (multiplier, decay) in the
+    merge, and ``_update`` states the choice of launch per arena once — flat or grouped, each with or without the
+    coefficient.  ``step`` with clipping: every arena's gradients complete, the chunk sums (one launch per arena), one
+    finalize for all sets, then the updates.  Nothing comes back to the host: the coefficients are read by the update
+    kernels from device memory."""
+    type = 'adamw'
+    _STATE = (('moment1', '_m'), ('moment2', '_v'))
 
     def __init__(self, learning_rate=0.001, beta1=0.9, beta2=0.999, epsilon=1e-08, parameters=None,
                  weight_decay=0.01, lr_ratio=None, apply_decay_param_fun=None, grad_clip=None,
@@ -393,120 +466,43 @@ class AdamW(_DeviceHyper):
         self._wd = float(weight_decay) if weight_decay else 0.0
         if self._wd < 0:
             raise ValueError('weight_decay must be >= 0, got %r' % (weight_decay,))
-        # one (parameter, multiplier, decay) per listed trainable parameter
-        listed = []
-        parameters = list(parameters or [])
-        if parameters and all(isinstance(g, dict) for g in parameters):
-            for gi, group in enumerate(parameters):
-                unknown = [k for k in group if k not in self._GROUP_KEYS]
-                if unknown or 'params' not in group:
-                    raise ValueError('parameter group %d: keys %r (known: %r, params required)'
-                                     % (gi, sorted(group), self._GROUP_KEYS))
-                if 'learning_rate' in group and 'lr_scale' in group:
-                    raise ValueError('parameter group %d gives its multiplier twice (learning_rate and lr_scale)' % gi)
-                scale = float(group.get('learning_rate', group.get('lr_scale', 1.0)))
-                wd = group.get('weight_decay', None)
-                wd = self._wd if wd is None else float(wd)
-                if wd < 0:
-                    raise ValueError('parameter group %d: weight_decay must be >= 0, got %r' % (gi, wd))
-                listed += [(p, scale, wd, gi) for p in group['params'] if p.requires_grad]
-        elif any(isinstance(g, dict) for g in parameters):
-            raise ValueError('parameters: a list of tensors or a list of group dicts, not a mixture')
-        else:
-            listed = [(p, 1.0, self._wd, 0) for p in parameters if p.requires_grad]
-        arenas = []
-        seen = {}
-        for p, _s, _w, _g in listed:
-            a = getattr(p, '_passl_arena', None)
-            if a is None:
-                raise NotImplementedError('AdamW optimises parameters that live in an EncoderArena')
-            if id(p) in seen:
-                raise ValueError('a parameter appears more than once in the parameter list / groups')
-            seen[id(p)] = True
-            if a not in arenas:
-                arenas.append(a)
-        for a in arenas:
-            if sum(1 for p, _s, _w, _g in listed if p._passl_arena is a) != len(a.param_slices):
-                raise NotImplementedError('optimising a subset of an arena is not supported')
-        self._parameter_list = [p for p, _s, _w, _g in listed]
-        self._arenas = arenas
-        self._param_table = []         # per arena: [(paddle auto-name, multiplier, decay)] in arena order
+        self._grad_clip = grad_clip
+        self._t = 0
+        listed = _listed_parameters(parameters, self._wd)
+        self._init_arenas([p for p, _s, _w, _g in listed])
+        arenas = self._arenas
+        names = [_paddle_auto_names(a) for a in arenas]
+        assert all(len(n) == len(a.param_slices) for n, a in zip(names, arenas))
+        per_arena = [_arena_rows(n, [e for e in listed if e[0]._passl_arena is a], lr_ratio, apply_decay_param_fun,
+                                 grad_clip) for n, a in zip(names, arenas)]
+        self._param_table = [rows for rows, _sets in per_arena]    # per arena: [(auto-name, multiplier, decay)]
+        self._param_sets = [sets for _rows, sets in per_arena]     # per arena: the clip set of every parameter
+        runs = [_clip_runs(a.param_slices, a.n_train, sets) for a, sets in zip(arenas, self._param_sets)]
+        launches = [_flat_or_segments(a.param_slices, a.n_train, rows, sets if any(runs) else None)
+                    for a, (rows, sets) in zip(arenas, per_arena)]
+        # device tables from here on
+        self._clip = None              # ops.grad_clip_plan over all arenas, or None: nothing is clipped
+        if any(runs):
+            n_sets = 1 if grad_clip.scope == 'global' else max(g for _p, _s, _w, g in listed) + 1
+            self._clip = ops.grad_clip_plan(runs, [a.n_train for a in arenas], n_sets, arenas[0].device)
         self._tables = []              # per arena: None (flat kernel with _flat_wd) or the device table
         self._flat_wd = []
-        # clipping (core/grad_clip.py): the set of every parameter — its group ('group' scope; a plain list is group 0)
-        # or 0 ('global'), -1 when the parameter is left out — then per arena the runs of equal set for the chunk table
-        self._grad_clip = grad_clip
-        self._clip = None              # ops.grad_clip_plan over all arenas, or None: nothing is clipped
         self._clip_coef = []           # per arena: the device float of its one set (flat clip launch) or None
-        n_sets = 1 if grad_clip is None or grad_clip.scope == 'global' else max([g for _p, _s, _w, g in listed] + [0]) + 1
-        param_sets, runs = [], []
-        for a in arenas:
-            names = _paddle_auto_names(a)
-            assert len(names) == len(a.param_slices)
-            rows = [None] * len(names)
-            sets = [-1] * len(names)
-            for p, scale, wd, gi in listed:
-                if p._passl_arena is not a:
-                    continue
-                name = names[p._passl_index]
-                if grad_clip is not None and not grad_clip.excludes(p, name):
-                    sets[p._passl_index] = 0 if grad_clip.scope == 'global' else gi
-                if lr_ratio is not None:
-                    scale = scale * float(lr_ratio(p))
-                if apply_decay_param_fun is not None and not apply_decay_param_fun(name):
-                    wd = 0.0
-                rows[p._passl_index] = (name, scale, wd)
-            self._param_table.append(rows)
-            param_sets.append(sets)
-            ends = [off for off, _n in a.param_slices[1:]] + [a.n_train]
-            starts = [off for off, _n in a.param_slices]
-            run = []
-            for start, end, st in zip(starts, ends, sets):
-                if st < 0:
-                    continue
-                if run and run[-1][1] == start and run[-1][2] == st:
-                    run[-1] = (run[-1][0], end, st)
-                else:
-                    run.append((start, end, st))
-            runs.append(run)
-        if grad_clip is not None and any(runs):
-            self._clip = ops.grad_clip_plan(runs, [a.n_train for a in arenas], n_sets,
-                                            arenas[0].device if arenas else torch.device('cpu'))
-        self._param_sets = param_sets
-        for a, rows, sets in zip(arenas, self._param_table, param_sets):
-            one_set = len(set(sets)) == 1
-            if self._clip is not None and one_set and sets[0] < 0:
-                sets = None                                  # nothing of this arena is clipped: today's launches
-            if self._clip is None:
-                sets = None
-            if all(s == 1.0 for _n, s, _w in rows) and len({w for _n, _s, w in rows}) == 1 \
-                    and (sets is None or one_set):
-                self._tables.append(None)
-                self._flat_wd.append(rows[0][2])
-                self._clip_coef.append(None if sets is None else self._clip['out'][sets[0], 1:])
-                continue
-            ends = [off for off, _n in a.param_slices[1:]] + [a.n_train]
-            seg_end, seg_scale, seg_wd, seg_set = [], [], [], []
-            for end, (_name, scale, wd), st in zip(ends, rows, sets or [-1] * len(rows)):
-                if seg_end and (seg_scale[-1], seg_wd[-1], seg_set[-1]) == (scale, wd, st):
-                    seg_end[-1] = end
-                else:
-                    seg_end.append(end)
-                    seg_scale.append(scale)
-                    seg_wd.append(wd)
-                    seg_set.append(st)
-            if sets is None:
-                self._tables.append(ops.adamw_groups_table(seg_end, seg_scale, seg_wd, a.n_train, a.device))
+        for a, (flat, segments) in zip(arenas, launches):
+            if flat is not None:
+                wd, st = flat
+                table, coef = None, None if st is None else self._clip['out'][st, 1:]
             else:
-                self._tables.append(ops.adamw_groups_clip_table(seg_end, seg_scale, seg_wd, seg_set, a.n_train,
-                                                                self._clip['n_sets'], a.device))
-            self._flat_wd.append(None)
-            self._clip_coef.append(None)
-        self._m = [torch.zeros_like(a.flat[:a.n_train]) for a in arenas]
-        self._v = [torch.zeros_like(a.flat[:a.n_train]) for a in arenas]
-        self._t = 0
-        self.grad_scale = 1.0
-        self._init_hyper(arenas[0].device if arenas else torch.device('cpu'))
+                wd, coef = None, None
+                seg_end, seg_scale, seg_wd, seg_set = segments
+                if seg_set is None:
+                    table = ops.adamw_groups_table(seg_end, seg_scale, seg_wd, a.n_train, a.device)
+                else:
+                    table = ops.adamw_groups_clip_table(seg_end, seg_scale, seg_wd, seg_set, a.n_train,
+                                                        self._clip['n_sets'], a.device)
+            self._tables.append(table)
+            self._flat_wd.append(wd)
+            self._clip_coef.append(coef)
 
     @property
     def grouped(self):
@@ -522,50 +518,37 @@ class AdamW(_DeviceHyper):
         self._t += 1
         return self.get_lr(), self._b1 ** self._t, self._b2 ** self._t
 
-    def get_lr(self):
-        lr = self._learning_rate
-        return float(lr()) if isinstance(lr, LRScheduler) else float(lr)
-
-    def clear_grad(self, set_to_zero=True):
-        for a in self._arenas:
-            a.clear_grad()
-
-    clear_gradients = clear_grad
+    def _update(self, i, hyper):
+        """The update launch of arena i: flat or grouped, each with or without a clip coefficient."""
+        a, m, v, table, coef = self._arenas[i], self._m[i], self._v[i], self._tables[i], self._clip_coef[i]
+        p = a.flat[:a.n_train]
+        if table is None and coef is None:
+            ops.adamw_dev(p, a.grads, m, v, hyper, self._b1, self._b2, self._eps, self._flat_wd[i], self.grad_scale)
+        elif table is None:
+            ops.adamw_clip_dev(p, a.grads, m, v, hyper, coef, self._b1, self._b2, self._eps, self._flat_wd[i],
+                               self.grad_scale)
+        elif 'seg_set' not in table:
+            ops.adamw_groups_dev(p, a.grads, m, v, table, hyper, self._b1, self._b2, self._eps, self.grad_scale)
+        else:
+            ops.adamw_groups_clip_dev(p, a.grads, m, v, table, hyper, self._clip['out'], self._b1, self._b2, self._eps,
+                                      self.grad_scale)
 
     @torch.no_grad()
     def step(self):
         hyper = self._hyper_for_step()
-        if self._clip is not None:
-            return self._step_clipped(hyper)
-        for a, m, v, table, wd in zip(self._arenas, self._m, self._v, self._tables, self._flat_wd):
-            _grads_complete(a)
-            if table is None:
-                ops.adamw_dev(a.flat[:a.n_train], a.grads, m, v, hyper, self._b1, self._b2, self._eps, wd,
-                              self.grad_scale)
-            else:
-                ops.adamw_groups_dev(a.flat[:a.n_train], a.grads, m, v, table, hyper, self._b1, self._b2, self._eps,
-                                     self.grad_scale)
-
-    def _step_clipped(self, hyper):
-        """Every arena's gradients complete, then: the chunk sums (one launch per arena), one finalize for all sets, the
-        updates.  Nothing comes back to the host: the coefficients are read by the update kernels from device memory."""
         clip, gc = self._clip, self._grad_clip
+        if clip is None:
+            for i, a in enumerate(self._arenas):
+                _grads_complete(a)
+                self._update(i, hyper)
+            return
         for a in self._arenas:
             _grads_complete(a)
         for b, a in enumerate(self._arenas):
             ops.grad_sumsq(a.grads, clip, b, self.grad_scale)
         ops.grad_clip_finalize(clip, gc.clip_norm, gc.clip_norm_max, gc.always_clip)
-        for a, m, v, table, wd, coef in zip(self._arenas, self._m, self._v, self._tables, self._flat_wd, self._clip_coef):
-            p = a.flat[:a.n_train]
-            if table is None and coef is None:
-                ops.adamw_dev(p, a.grads, m, v, hyper, self._b1, self._b2, self._eps, wd, self.grad_scale)
-            elif table is None:
-                ops.adamw_clip_dev(p, a.grads, m, v, hyper, coef, self._b1, self._b2, self._eps, wd, self.grad_scale)
-            elif 'seg_set' not in table:
-                ops.adamw_groups_dev(p, a.grads, m, v, table, hyper, self._b1, self._b2, self._eps, self.grad_scale)
-            else:
-                ops.adamw_groups_clip_dev(p, a.grads, m, v, table, hyper, clip['out'], self._b1, self._b2, self._eps,
-                                          self.grad_scale)
+        for i in range(len(self._arenas)):
+            self._update(i, hyper)
 
     def grad_norms(self):
         """The device table [n_sets, 2] = {norm, coef} of the last step's sets (set = parameter group under the 'group'
@@ -578,18 +561,8 @@ class AdamW(_DeviceHyper):
         return [(row[0], st) for rows, sets in zip(self._param_table, self._param_sets) for row, st in zip(rows, sets)]
 
     def state_dict(self):
-        sd = {'t': self._t}
-        for i, (m, v) in enumerate(zip(self._m, self._v)):
-            sd['moment1_%d' % i] = m.detach().cpu()
-            sd['moment2_%d' % i] = v.detach().cpu()
-        if isinstance(self._learning_rate, LRScheduler):
-            sd['LR_Scheduler'] = self._learning_rate.state_dict()
-        return sd
+        return dict(super().state_dict(), t=self._t)
 
     def set_state_dict(self, sd):
         self._t = int(sd['t'])
-        for i, (m, v) in enumerate(zip(self._m, self._v)):
-            _load_flat_state(m, sd, 'moment1_%d' % i)
-            _load_flat_state(v, sd, 'moment2_%d' % i)
-        if 'LR_Scheduler' in sd and isinstance(self._learning_rate, LRScheduler):
-            self._learning_rate.set_state_dict(sd['LR_Scheduler'])
+        super().set_state_dict(sd)

@@ -64,6 +64,25 @@ def test_uniform_table_equals_the_flat_kernel_bit_for_bit(n, n_seg):
     assert not torch.equal(pa, p0)
 
 
+@pytest.mark.parametrize('n', [1, 3, 4099, 2 ** 20 + 27, 2 ** 21 + 2 ** 19 + 27])
+def test_scalars_by_value_and_from_device_memory_give_equal_bits_with_a_tail(n):
+    """ops.adamw (lr, beta^t by value) against ops.adamw_dev (the same floats, rounded to fp32, read from device memory)
+    on an n that is no multiple of 4: the last n % 4 elements take the flat kernel's scalar tail, which no
+    variant-against-variant test reaches (their n are multiples of 4).  Tail only (1, 3), a tail after 1024 float4
+    (4099), after 1025 workgroups of one grid round (2**20 + 27) and after the capped grid of 2048 workgroups went
+    round more than once (2**21 + 2**19 + 27 = 655366 float4 > 2048 * 256)."""
+    from passl_amd.hip import ops
+    p0, grads = _buffers(n, 13)
+    pa, pb = p0.clone(), p0.clone()
+    ma, va, mb, vb = (torch.zeros(n, device=DEV) for _ in range(4))
+    for t, g in enumerate(grads, 1):
+        lr = LR * (1.0 - 0.1 * t)
+        ops.adamw(pa, g, ma, va, lr, B1, B2, EPS, 0.05, B1 ** t, B2 ** t, 0.5)
+        ops.adamw_dev(pb, g, mb, vb, _hyper(t, lr), B1, B2, EPS, 0.05, 0.5)
+        assert torch.equal(_bits(pa), _bits(pb)) and torch.equal(_bits(ma), _bits(mb)) and torch.equal(_bits(va), _bits(vb))
+    assert not torch.equal(pa[-1:], p0[-1:]) and bool((ma[-(n & 3):] != 0).all())      # the tail was updated
+
+
 # ---------------------------------------------------------------------------------------------- 2. groups = slices
 LENGTHS = [4, 8, 12, 1000, 4096, 4100, 65540]
 

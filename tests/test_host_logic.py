@@ -1,6 +1,7 @@
 """Host-side mirror of the reference interface, exercised on CPU: registries, config +
 overrides, lr schedule, hook bus order, Trainer loop, model construction / state_dict layout.
 (The HIP layers are built but not run here; running them needs the GPU tests.)"""
+import functools
 import math
 import os
 
@@ -489,6 +490,88 @@ def test_checkpoint_file_format_and_extract_weight(tmp_path):
     from passl_amd.utils.checkpoint import to_numpy, to_tensors
     opt2.set_state_dict(to_tensors(to_numpy(opt.state_dict())))
     assert torch.equal(opt2._velocity[0], opt._velocity[0]) and sched2.last_epoch == 5 and sched2() == sched()
+
+
+@functools.lru_cache(maxsize=None)
+def _moco_cpu_model():
+    """One MoCo model on the CPU (the one of test_checkpoint_file_format_and_extract_weight) for the four cases below:
+    they only read its arena."""
+    hip_config.set_device('cpu')
+    import moco_util as U
+    from passl_amd.modeling import build_model
+    cfg = dict(U.MODEL_CFG)
+    cfg.update(K=256)
+    torch.manual_seed(3)
+    return build_model(cfg)
+
+
+@pytest.mark.parametrize('name, kwargs, vectors', [
+    ('Momentum', dict(momentum=0.9, weight_decay=1e-4), ['velocity']),
+    ('LarsMomentumOptimizer', dict(momentum=0.9, lars_weight_decay=1e-6), ['velocity']),
+    ('MomentumLARC', dict(momentum=0.9, weight_decay=1e-6), ['velocity']),
+    ('AdamW', dict(weight_decay=0.05), ['moment1', 'moment2'])])
+def test_optimizer_state_dict_keys_round_trip_and_refusals(name, kwargs, vectors):
+    """The checkpoint layout of the four arena optimizers: one flat vector per arena under ``<name>_<arena index>``,
+    AdamW's step count ``t``, the scheduler under ``LR_Scheduler`` (only when a scheduler drives the rate) — nothing
+    else, so a file written before the optimizers shared a base class loads.  A vector of another size is a ValueError,
+    a missing one a KeyError; a parameter listed twice is a ValueError from every one of them.  (The Momentum round trip through the checkpoint pickle is part of
+    test_checkpoint_file_format_and_extract_weight; AdamW's key set without a scheduler is also asserted in
+    test_adamw_groups_host.py and test_grad_clip_host.py.)"""
+    from passl_amd.solver import OPTIMIZERS
+    from passl_amd.solver.lr_scheduler import CosineAnnealingDecay
+    model = _moco_cpu_model()
+    cls = OPTIMIZERS.get(name)
+    plist = 'parameter_list' if name == 'LarsMomentumOptimizer' else 'parameters'
+
+    def make(lr):
+        return cls(lr, **dict(kwargs, **{plist: list(model.parameters())}))
+    with pytest.raises(ValueError, match='more than once'):                # a parameter listed twice: all four alike
+        cls(0.1, **dict(kwargs, **{plist: list(model.parameters()) + list(model.parameters())[:1]}))
+    keys = {'%s_0' % v for v in vectors} | ({'t'} if name == 'AdamW' else set())
+    assert set(make(0.1).state_dict()) == keys                             # a float rate: no scheduler entry
+    sched = CosineAnnealingDecay(0.015, T_max=100)
+    opt = make(sched)
+    assert len(opt._arenas) == 1
+    gen = torch.Generator().manual_seed(5)
+    state = [getattr(opt, {'velocity': '_velocity', 'moment1': '_m', 'moment2': '_v'}[v])[0] for v in vectors]
+    for x in state:
+        x.copy_(torch.randn(x.numel(), generator=gen))
+    if name == 'AdamW':
+        opt._t = 7
+    for _ in range(5):
+        sched.step()
+    sd = opt.state_dict()
+    assert set(sd) == keys | {'LR_Scheduler'}
+    assert all(sd['%s_0' % v].shape == (opt._arenas[0].n_train,) and sd['%s_0' % v].device.type == 'cpu' for v in vectors)
+    sched2 = CosineAnnealingDecay(0.015, T_max=100)
+    opt2 = make(sched2)
+    opt2.set_state_dict(sd)
+    sd2 = opt2.state_dict()
+    assert set(sd2) == set(sd) and all(torch.equal(sd2['%s_0' % v], sd['%s_0' % v]) for v in vectors)
+    assert all(bool(sd['%s_0' % v].any()) for v in vectors)
+    assert sched2.last_epoch == 5 and sched2() == sched() and opt2.get_lr() == opt.get_lr()
+    if name == 'AdamW':
+        assert sd2['t'] == 7 and opt2._t == 7
+    for v in vectors:
+        short = dict(sd)
+        short['%s_0' % v] = sd['%s_0' % v][:-1]
+        with pytest.raises(ValueError, match='elements'):
+            opt2.set_state_dict(short)
+        missing = {k: x for k, x in sd.items() if k != '%s_0' % v}
+        with pytest.raises(KeyError, match='%s_0' % v):
+            opt2.set_state_dict(missing)
+
+
+def test_asm_diff_reports_an_unchanged_stream_under_a_new_name_as_renamed():
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, 'tools'))
+    import asm_diff
+    old = {'same': ['a'], 'edited': ['b'], 'folded': ['c', 'd'], 'dropped': ['e']}
+    new = {'same': ['a'], 'edited': ['B'], 'template<0>': ['c', 'd'], 'added': ['f']}
+    assert asm_diff.match(old, new) == (['edited'], {'folded': 'template<0>'}, ['dropped'], ['added'])
+    # one new kernel answers for one old kernel only; an old name that is still there is never "renamed"
+    assert asm_diff.match({'x': ['a'], 'y': ['a']}, {'z': ['a']}) == ([], {'x': 'z'}, ['y'], [])
+    assert asm_diff.match({'x': ['a']}, {'x': ['b'], 'z': ['a']}) == (['x'], {}, [], ['z'])
 
 
 # ------------------------------------------------------------------ MAE / CLIP rows (host side)

@@ -1,6 +1,10 @@
 """Is the device code of the kernels unchanged?  Compiles every HIP source of passl_amd/csrc at a given commit and in
 the working tree to gfx950 assembly (same flags as the build) and compares the instruction streams kernel by kernel
-(comments, debug lines and basic-block label numbers ignored).  Runs without a GPU.
+(comments, debug lines and basic-block label numbers ignored).  A kernel whose name is gone while a new name carries
+its instruction stream unchanged is reported as renamed, not as changed.  The compared stream runs to the end of the
+kernel's descriptor (kernarg size, register counts), and the offsets of the hidden arguments follow the explicit ones:
+a kernel folded into a template with another parameter list therefore comes out as removed + new, never as renamed.
+Runs without a GPU.
 
     python tools/asm_diff.py <commit>        # e.g. the last commit whose build passed the GPU suite
 
@@ -31,7 +35,8 @@ def kernels(path):
                 continue
             s = re.sub(r'\s*;.*$', '', line).rstrip()
             if s.strip() and not s.strip().startswith(('.loc', '.file', '.cfi')):
-                buf.append(re.sub(r'\.LBB\d+_', '.LBB_', s))
+                # (the kernel's own name, which its descriptor and section lines carry: a rename alone is no change)
+                buf.append(re.sub(r'\.LBB\d+_', '.LBB_', s).replace(cur, '<kernel>'))
     return out
 
 
@@ -40,6 +45,24 @@ def assemble(src, dst):
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(r.stderr[-2000:])
+
+
+def match(a, b):
+    """{name: stream} of the old and the new build -> (different, renamed {old: new}, removed, new).  Renamed: the old
+    name is gone and a new name carries its instruction stream unchanged (a kernel folded into a template, say)."""
+    diff = [n for n in a if n in b and a[n] != b[n]]
+    new = [n for n in b if n not in a]
+    renamed = {}
+    for n in a:
+        twin = [k for k in new if n not in b and k not in renamed.values() and b[k] == a[n]]
+        if twin:
+            renamed[n] = twin[0]
+    gone = [n for n in a if n not in b and n not in renamed]
+    return diff, renamed, gone, [n for n in new if n not in renamed.values()]
+
+
+def demangle(name):
+    return subprocess.run(['c++filt', name], capture_output=True, text=True).stdout.strip()[:140]
 
 
 def main():
@@ -59,13 +82,15 @@ def main():
             assemble(po, os.path.join(tmp, 'a.s'))
             assemble(os.path.join(B.HERE, s), os.path.join(tmp, 'b.s'))
             a, b = kernels(os.path.join(tmp, 'a.s')), kernels(os.path.join(tmp, 'b.s'))
-            diff = [n for n in a if n in b and a[n] != b[n]]
-            gone = [n for n in a if n not in b]
-            new = [n for n in b if n not in a]
+            diff, renamed, gone, new = match(a, b)
             changed += len(diff) + len(gone)
-            print('%-24s %3d kernels: %3d identical, %d different, %d removed, %d new' % (s, len(a), len(a) - len(diff) - len(gone), len(diff), len(gone), len(new)))
-            for n in diff + gone:
-                print('    ' + subprocess.run(['c++filt', n], capture_output=True, text=True).stdout.strip()[:140])
+            print('%-24s %3d kernels: %3d identical, %d renamed, %d different, %d removed, %d new'
+                  % (s, len(a), len(a) - len(diff) - len(gone) - len(renamed), len(renamed), len(diff), len(gone), len(new)))
+            for n, k in renamed.items():
+                print('    renamed   %s -> %s' % (demangle(n), demangle(k)))
+            for tag, names in (('different', diff), ('removed', gone), ('new', new)):
+                for n in names:
+                    print('    %-9s %s' % (tag, demangle(n)))
         print('# %s' % ('every kernel of the old build is unchanged' if changed == 0 else '%d kernels changed' % changed))
 
 
