@@ -11,7 +11,9 @@
 // plus two wave shuffles (lanes l, l^16, l^32 share a row).  The probability tile is then already
 // in the A-operand layout of the second MFMA (P x V, dS x K, P^T x dO, dS^T x Q).
 // Backward = two sweeps: own query rows x swept keys -> dQ;  own key columns x swept queries ->
-// dK, dV (P is recomputed from the saved row log-sum-exp; delta_i = dO_i . O_i).
+// dK, dV (P is recomputed from the saved row log-sum-exp; delta_i = dO_i . O_i).  The recomputation rounds
+// s * scale before it subtracts lse, as the forward did before it formed lse: fused into one fma it keeps the
+// product's rounding error, |s| 2^-24, as a relative error of every P (a lone key's P is then not 1).
 // `causal` (CLIP text tower, passl_v110/modeling/backbones/clip.py:284-286: additive triu(-inf, 1)
 // mask): key j is visible to query i iff j <= i; fully masked tiles are skipped.
 // Limits: d in {32, 64}, T <= 208 (13 tiles) — the MAE pre-training shapes; larger T needs a
@@ -37,6 +39,12 @@ constexpr int kMaxTiles = 13;
 constexpr float kNeg = -1e30f;
 
 __device__ __forceinline__ float shx(float v, int m) { return __shfl_xor(v, m, 64); }
+
+// a * b rounded to fp32 before anything is done with it: never the multiplier of an fma
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
 
 template <typename T> __device__ __forceinline__ float ldf(const T* p);
 template <> __device__ __forceinline__ float ldf<float>(const float* p) { return *p; }
@@ -230,7 +238,7 @@ __global__ void __launch_bounds__(kThreads) attn_bwd_q_kernel(
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const bool cv = rv && (ct * 16 + l4 * 4 + r <= lim);
-        const float p = cv ? __expf(s[r] * scale - l) : 0.f;
+        const float p = cv ? __expf(mul_rn(s[r], scale) - l) : 0.f;   // rounded product, as under lse
         ds[r] = p * (dp[r] - delta) * scale;
       }
       accum_tile<DH>(ds, Ks, ct, l15, l4, dq);
@@ -295,7 +303,7 @@ __global__ void __launch_bounds__(kThreads) attn_bwd_kv_kernel(
       for (int r = 0; r < 4; ++r) {
         const int row = rt * 16 + l4 * 4 + r;
         const bool ok = cv && row < Tn && (!causal || row >= col);
-        p[r] = ok ? __expf(s[r] * scale - Ls[row]) : 0.f;
+        p[r] = ok ? __expf(mul_rn(s[r], scale) - Ls[row]) : 0.f;
         ds[r] = p[r] * (dp[r] - Dl[row]) * scale;
       }
       accum_tile<DH>(p, Ds, rt, l15, l4, dv);
