@@ -287,6 +287,31 @@ typedef struct passl_conv_desc {
 } passl_conv_desc;
 int passl_hip_conv_igemm(const passl_conv_desc* d, passl_stream_t stream);
 
+/* The same launch with a transform of the A operand on its way into the kernel ("A-operand prologue"): the apply pass of
+ * the BatchNorm whose output the convolution consumes, done by the convolution.  The kernel reads the BatchNorm's INPUT
+ * as `d->a`, transforms every 8-channel chunk with the arithmetic of passl_hip_bn_apply / passl_hip_bn_bwd_apply (the
+ * same device functions: bit-identical values), multiplies with the transformed chunk, and — workgroups of the first
+ * column block only — stores it once to `a_out` (dense, same shape and dtype as `d->a`), where the weight gradient reads
+ * it later.  a_out must not alias d->a or d->y.
+ *   PASSL_APRO_BN_FWD  a_out = relu(a * a_scale[c] + a_shift[c])                    (a_scale, a_shift: fp32 [C])
+ *   PASSL_APRO_BN_BWD  a_out = a_coef[c] * a + a_coef[C + c] * a2 + a_coef[2C + c]  (a = masked gradient g, a2 = the
+ *                      BatchNorm's input, addressed like a; a_coef: the fp32 [3][C] of passl_hip_bn_bwd_finalize)
+ * Everything else (epilogue, fused statistics, bnb_*) is passl_hip_conv_igemm's.  Served by the register-staged kernel
+ * only: bf16, dense 1x1 / stride 1 / pad 0 launches with C % 64 == 0 and C < 512 and bf16 output, without bnb2_*;
+ * BN_FWD with NCOLS > 64, BN_BWD with NCOLS <= 64 (one column block: every chunk is loaded once), not with option
+ * igemm_persist.  Anything else: PASSL_EUNSUPPORTED and nothing is launched — run the streaming pass and
+ * passl_hip_conv_igemm instead. */
+enum passl_apro_mode { PASSL_APRO_BN_FWD = 1, PASSL_APRO_BN_BWD = 2 };
+typedef struct passl_conv_apro {
+  const void* a2;
+  const float* a_scale;
+  const float* a_shift;
+  const float* a_coef;
+  void* a_out;
+  int32_t mode;            /* passl_apro_mode */
+} passl_conv_apro;
+int passl_hip_conv_igemm_apro(const passl_conv_desc* d, const passl_conv_apro* pro, passl_stream_t stream);
+
 /* Weight gradient:  dw[col][r][s][c] += sum_{n,op,oq} dy[n,op,oq,col] * A[n, op*sh+r-ph, oq*sw+s-pw, c]
  * dw is fp32 [NCOLS][R*S*C] and is ACCUMULATED into (caller zeroes it).
  * dy is [M][NCOLS] dense (row stride dy_ld elements).  `splits` = number of M-slices (>=1): every

@@ -13,6 +13,7 @@
 // bwd_reduce 6, bwd_apply 8 (+2 with residual).
 #include <mutex>
 #include "common.h"
+#include "bn_chunk.h"
 #include "options.h"
 
 namespace {
@@ -557,8 +558,7 @@ __global__ void __launch_bounds__(kThreads) bn_apply_tile_kernel(const T* __rest
   for (int u = 0; u < U; ++u) {
     const int64_t i = base + u * kThreads;
     if (i >= nchunks) break;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[u][e] = v[u][e] * sc[e] + sh[e];
+    bnc::affine8(v[u], sc, sh);
     if (res) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[u][e] += r[u][e];
@@ -570,8 +570,7 @@ __global__ void __launch_bounds__(kThreads) bn_apply_tile_kernel(const T* __rest
         for (int e = 0; e < 8; ++e) bits |= (v[u][e] > 0.f ? 1u : 0u) << e;
         mask[i] = (uint8_t)bits;
       }
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[u][e] = fmaxf(v[u][e], 0.f);
+      bnc::relu8(v[u]);
     }
     ElemTraits<T>::store8(z + i * 8, v[u]);
   }
@@ -614,8 +613,7 @@ __global__ void __launch_bounds__(kThreads) bn_bwd_apply_tile_kernel(
     if (i >= nchunks) break;
     if (relu) apply_relu_mask<T>(g[u], v[u], relu, z, i, sc, sh);
     float o[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = cA[e] * g[u][e] + cB[e] * v[u][e] + cC[e];
+    bnc::bwd8(o, g[u], v[u], cA, cB, cC);
     ElemTraits<T>::store8(dx + i * 8, o);
     if (dres) ElemTraits<T>::store8(dres + i * 8, g[u]);
   }

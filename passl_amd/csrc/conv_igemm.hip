@@ -36,6 +36,7 @@
 //   that stay live across the epilogue cost the kernel half its workgroups per CU (229 VGPRs: 2 instead of 3-4), and the
 //   store phase is bound by how many waves issue stores, not by their acknowledgements.  OPT-IN (igemm_persist=1).
 #include "common.h"
+#include "bn_chunk.h"
 #include "igemm_epi.h"
 #include "options.h"
 #include "prof.h"
@@ -99,15 +100,33 @@ struct Params {
   int dbg;   // ablation switches for tuning runs (option igemm_dbg): 1 no stores, 2 no epilogue, 4 no A loads, 8 no MFMA
 };
 
+// A-operand prologue (APRO instantiations, dense bf16 only): the A chunk is transformed in its staging register on the way
+// to LDS — a BatchNorm's apply pass done by the convolution that consumes its output (csrc/bn_chunk.h: the streaming
+// kernels' own arithmetic) — and the workgroups of column block 0 store the transformed chunk to a_out at the chunk's
+// dense offset, for the weight gradient that reads the same tensor later.
+//   APRO = 1 (forward):  A = y;        chunk = relu(y * a_scale + a_shift)
+//   APRO = 2 (backward): A = g, a2 = y; chunk = cA * g + cB * y + cC, a_coef = [3][C]; launches of ONE column block only
+struct ParamsA : Params {
+  const char* a2;
+  const float* a_scale;
+  const float* a_shift;
+  const float* a_coef;
+  char* a_out;
+};
+template <int APRO> struct ParamsOf { typedef ParamsA type; };
+template <> struct ParamsOf<0> { typedef Params type; };
+
 __device__ __forceinline__ int swz(int row, int slot) { return slot ^ ((row >> 1) & 7); }
 
 // DENSE: 1x1 / stride 1 / no padding with dense A and Y: row m lives at m*C resp. m*NCOLS, no
 // (n,op,oq) decomposition at all.
 template <typename T, int BM, int BN, bool GENERIC, int STAGES, bool EPI32, bool DENSE, bool LEAN = false, bool BNB2 = false,
-          bool PERSIST = false>
+          bool PERSIST = false, int APRO = 0>
 __global__ void __launch_bounds__(kThreads, PERSIST ? 2 : (LEAN ? 4 : ((STAGES == 1 && !EPI32) ? 3 : 2)))
-    igemm_kernel(const Params p) {
+    igemm_kernel(const typename ParamsOf<APRO>::type p) {
   static_assert(!PERSIST || (DENSE && STAGES == 1 && !EPI32 && !GENERIC), "persistent form: dense bf16 launches");
+  static_assert(APRO == 0 || (DENSE && STAGES == 1 && !EPI32 && !GENERIC && !PERSIST && sizeof(T) == 2),
+                "A-operand prologue: dense bf16 launches of the single-stage form");
   constexpr int ES = sizeof(T);
   constexpr int VEC = 16 / ES;          // elements per 16-byte slot
   constexpr int BK = kRowBytes / ES;    // elements per K-tile
@@ -198,6 +217,12 @@ __global__ void __launch_bounds__(kThreads, PERSIST ? 2 : (LEAN ? 4 : ((STAGES =
   set_rowoff(m0);
 
   uint4 ra[ACH], rb[BCH];
+  // APRO: the second A stream (backward); the per-channel constants ([2][C] scale, shift / [3][C] coef) sit in LDS
+  // behind the row table — kept in registers across the MFMAs they cost the backward form a workgroup per CU
+  uint4 ra2[APRO == 2 ? ACH : 1];
+  constexpr int NCST = APRO == 0 ? 0 : (APRO == 1 ? 2 : 3);
+  float* cst = reinterpret_cast<float*>(smem + MAIN_BYTES + BM * 8);
+  int ld_c = 0;                            // first channel of this thread's chunks of the tile in ra
   const int nk = LEAN ? 1 : (p.KDIM + BK - 1) / BK;     // LEAN: single K-tile launches only
 
   auto load_tile = [&](int kt) {
@@ -227,9 +252,13 @@ __global__ void __launch_bounds__(kThreads, PERSIST ? 2 : (LEAN ? 4 : ((STAGES =
         const int64_t off = DENSE ? a_base[i] + c
                                   : a_base[i] + (int64_t)ih * p.a_sh + (int64_t)iw * p.a_sw + c;
         v = *reinterpret_cast<const uint4*>(p.a + off * ES);
+        if constexpr (APRO == 2) ra2[i] = *reinterpret_cast<const uint4*>(p.a2 + off * ES);
+      } else if constexpr (APRO == 2) {
+        ra2[i] = v;
       }
       ra[i] = v;
     }
+    if constexpr (APRO != 0) ld_c = c;
 #pragma unroll
     for (int j = 0; j < BCH; ++j) {
       const int col = ld_n0 + (tid >> 3) + 32 * j;
@@ -241,6 +270,35 @@ __global__ void __launch_bounds__(kThreads, PERSIST ? 2 : (LEAN ? 4 : ((STAGES =
     }
   };
   auto store_tile = [&](int buf) {
+    if constexpr (APRO != 0) {
+      // the transform of the rows that exist (rows m >= M stay zero and are not stored); column block 0 writes it back
+      float k0_[8], k1_[8], k2_[8];
+      const auto get = [&](float (&d)[8], int q) __attribute__((always_inline)) {
+        const float4 a = *reinterpret_cast<const float4*>(cst + q * p.C + ld_c);
+        const float4 b = *reinterpret_cast<const float4*>(cst + q * p.C + ld_c + 4);
+        d[0] = a.x; d[1] = a.y; d[2] = a.z; d[3] = a.w; d[4] = b.x; d[5] = b.y; d[6] = b.z; d[7] = b.w;
+      };
+      get(k0_, 0);
+      get(k1_, 1);
+      if constexpr (APRO == 2) get(k2_, 2);
+#pragma unroll
+      for (int i = 0; i < ACH; ++i) {
+        if (ih0[i] < 0) continue;
+        float v[8];
+        epi::unpack8(ra[i], v);
+        if constexpr (APRO == 1) {
+          bnc::affine8(v, k0_, k1_);
+          bnc::relu8(v);
+          ra[i] = epi::pack8(v);
+        } else {
+          float y[8], o[8];
+          epi::unpack8(ra2[i], y);
+          bnc::bwd8(o, v, y, k0_, k1_, k2_);
+          ra[i] = epi::pack8(o);
+        }
+        if (nt == 0) *reinterpret_cast<uint4*>(p.a_out + (a_base[i] + ld_c) * ES) = ra[i];
+      }
+    }
 #pragma unroll
     for (int i = 0; i < ACH; ++i) {
       const int row = (tid >> 3) + 32 * i;
@@ -310,6 +368,14 @@ __global__ void __launch_bounds__(kThreads, PERSIST ? 2 : (LEAN ? 4 : ((STAGES =
   };
 
   load_tile(0);
+  if constexpr (APRO != 0) {
+    // the constants, once per workgroup, under the first tile's loads
+    for (int i = tid * 4; i < NCST * p.C; i += kThreads * 4) {
+      const float* src = APRO == 1 ? (i < p.C ? p.a_scale + i : p.a_shift + (i - p.C)) : p.a_coef + i;
+      *reinterpret_cast<float4*>(cst + i) = *reinterpret_cast<const float4*>(src);
+    }
+    __syncthreads();
+  }
   if constexpr (PERSIST) {
     const int G = gridDim.x;
     for (;;) {
@@ -434,16 +500,19 @@ __global__ void __launch_bounds__(kThreads, PERSIST ? 2 : (LEAN ? 4 : ((STAGES =
 }
 
 template <typename T, int BM, int BN, bool GENERIC, int STAGES, bool EPI32, bool DENSE, bool LEAN = false, bool BNB2 = false,
-          bool PERSIST = false>
-int launch(const Params& p, hipStream_t st) {
+          bool PERSIST = false, int APRO = 0>
+int launch(const typename ParamsOf<APRO>::type& p, hipStream_t st) {
   constexpr int STAGE = STAGES * (BM + BN) * kRowBytes;
   constexpr int EPI = EPI32 ? BM * (BN + 4) * 4 : BM * (BN + 8) * 2;
   constexpr int LDS = (STAGE > EPI ? STAGE : EPI) + BM * 8;
-  const void* fn = reinterpret_cast<const void*>(&igemm_kernel<T, BM, BN, GENERIC, STAGES, EPI32, DENSE, LEAN, BNB2, PERSIST>);
+  const void* fn = reinterpret_cast<const void*>(&igemm_kernel<T, BM, BN, GENERIC, STAGES, EPI32, DENSE, LEAN, BNB2, PERSIST, APRO>);
+  // APRO: the per-channel constants take (2 or 3) x C floats of LDS behind the row table (C < 512)
+  constexpr int CST_MAX = APRO == 0 ? 0 : (APRO == 1 ? 2 : 3) * 448 * 4;
+  const int lds = LDS + (APRO == 0 ? 0 : (APRO == 1 ? 2 : 3) * p.C * 4);
   static bool attr_set = false;
   static int wg_slots = 0;               // PERSIST: resident workgroups of this instantiation on the whole device
   if (!attr_set) {
-    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS + CST_MAX);
     if (PERSIST) {
       int occ = 0, dev = 0, cus = 0;
       if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, kThreads, LDS) != hipSuccess || occ < 1) occ = 1;
@@ -457,8 +526,8 @@ int launch(const Params& p, hipStream_t st) {
   const int grid_opt = passl_opt(Opt::igemm_persist_grid) & ~7;      // 0: as many workgroups as the device holds
   const int slots = (PERSIST && grid_opt >= 8) ? grid_opt : wg_slots;
   const int grid = (PERSIST && p.ntiles > slots) ? slots : p.ntiles;
-  hipLaunchKernelGGL((igemm_kernel<T, BM, BN, GENERIC, STAGES, EPI32, DENSE, LEAN, BNB2, PERSIST>), dim3(grid),
-                     dim3(kThreads), LDS, st, p);
+  hipLaunchKernelGGL((igemm_kernel<T, BM, BN, GENERIC, STAGES, EPI32, DENSE, LEAN, BNB2, PERSIST, APRO>), dim3(grid),
+                     dim3(kThreads), lds, st, p);
   return hipGetLastError() == hipSuccess ? PASSL_OK : PASSL_ELAUNCH;
 }
 
@@ -504,7 +573,7 @@ int passl_conv3x3_wave_try(const passl_conv_desc* d, hipStream_t st); // conv3x3
 static int g_last_kernel = -1;
 extern "C" int passl_hip_last_igemm_kernel(void) { return g_last_kernel; }
 
-extern "C" int passl_hip_conv_igemm(const passl_conv_desc* d, passl_stream_t stream) {
+static int conv_igemm_impl(const passl_conv_desc* d, const passl_conv_apro* pro, passl_stream_t stream) {
   if (!d || !d->a || !d->b || !d->y) return PASSL_EINVAL;
   // fused BN statistics (forward or backward) live in the bf16-output epilogue only
   if (d->stats && (d->dtype != PASSL_BF16 || d->out_f32 || d->residual || d->bnb_partial ||
@@ -532,7 +601,8 @@ extern "C" int passl_hip_conv_igemm(const passl_conv_desc* d, passl_stream_t str
   const int64_t K64 = (int64_t)d->R * d->S * d->C;
   if (M64 > 0x7fffffff || K64 > 0x7fffffff) return PASSL_EINVAL;
 
-  Params p;
+  ParamsA p;
+  p.a2 = nullptr; p.a_scale = p.a_shift = p.a_coef = nullptr; p.a_out = nullptr;
   p.a = reinterpret_cast<const char*>(d->a);
   p.b = reinterpret_cast<const char*>(d->b);
   p.y = reinterpret_cast<char*>(d->y);
@@ -579,6 +649,34 @@ extern "C" int passl_hip_conv_igemm(const passl_conv_desc* d, passl_stream_t str
   const double w_bytes = in_px * d->C * es + (double)d->NCOLS * K64 * es +
                          (double)M64 * d->NCOLS * es_out * (1 + (d->residual ? 1 : 0)) +
                          (d->bnb_partial ? (double)M64 * d->NCOLS * es : 0.0);
+  if (pro) {
+    // A-operand prologue (passl_hip_conv_igemm_apro): the register-staged kernel's own instantiations, nothing else —
+    // the LDS-DMA kernels cannot transform an operand in flight.  Forward: 128-column tiles (NCOLS > 64); backward:
+    // ONE 64-column block, so that every chunk is loaded (and written back) exactly once.
+    const int nk = (p.KDIM + bk - 1) / bk;
+    const bool fwd = pro->mode == PASSL_APRO_BN_FWD;
+    if (d->dtype != PASSL_BF16 || d->out_f32 || !dense || generic || d->bnb2_partial || persist_on() || nk >= 8 ||
+        nk > passl_opt(Opt::igemm_nk1) || (fwd ? narrow : !narrow))
+      return PASSL_EUNSUPPORTED;
+    p.a2 = reinterpret_cast<const char*>(pro->a2);
+    p.a_scale = pro->a_scale; p.a_shift = pro->a_shift; p.a_coef = pro->a_coef;
+    p.a_out = reinterpret_cast<char*>(pro->a_out);
+    // the write-back of the transformed operand: one more pass of stores over A (and one of loads over a2)
+    const double a_bytes = in_px * d->C * es;
+    passl_prof_begin(2, st);
+    int rc2;
+    if (fwd) {
+      const bool lean = passl_opt(Opt::igemm_lean) && nk == 1 && !p.res && !p.bnb_partial;
+      rc2 = lean ? launch<bf16_t, 128, 128, false, 1, false, true, true, false, false, 1>(p, st)
+                 : launch<bf16_t, 128, 128, false, 1, false, true, false, false, false, 1>(p, st);
+    } else {
+      rc2 = launch<bf16_t, 128, 64, false, 1, false, true, false, false, false, 2>(p, st);
+    }
+    passl_prof_work(2, w_flops, w_bytes + a_bytes * (fwd ? 1 : 2));
+    passl_prof_end(2, st);
+    g_last_kernel = 0;
+    return rc2;
+  }
   if (d->bnb2_partial) {
     // two BatchNorm layers behind one gradient (passl_conv_desc.bnb2_*): its own instantiations of the register-staged
     // kernel (reductions below 8 K-tiles) and of the ring kernel, dense 1x1 launches only
@@ -639,4 +737,21 @@ extern "C" int passl_hip_conv_igemm(const passl_conv_desc* d, passl_stream_t str
   passl_prof_work(2, w_flops, w_bytes);
   passl_prof_end(2, st);
   return rc;
+}
+
+extern "C" int passl_hip_conv_igemm(const passl_conv_desc* d, passl_stream_t stream) {
+  return conv_igemm_impl(d, nullptr, stream);
+}
+
+extern "C" int passl_hip_conv_igemm_apro(const passl_conv_desc* d, const passl_conv_apro* pro, passl_stream_t stream) {
+  if (!d || !pro || !pro->a_out) return PASSL_EINVAL;
+  if (pro->mode == PASSL_APRO_BN_FWD) {
+    if (!pro->a_scale || !pro->a_shift || !aligned16(pro->a_scale) || !aligned16(pro->a_shift)) return PASSL_EINVAL;
+  } else if (pro->mode == PASSL_APRO_BN_BWD) {
+    if (!pro->a2 || !pro->a_coef || !aligned16(pro->a2) || !aligned16(pro->a_coef) || (d->C & 3)) return PASSL_EINVAL;
+  } else {
+    return PASSL_EINVAL;
+  }
+  if (!aligned16(pro->a_out) || pro->a_out == d->y || pro->a_out == d->a) return PASSL_EINVAL;
+  return conv_igemm_impl(d, pro, stream);
 }

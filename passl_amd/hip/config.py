@@ -27,7 +27,12 @@ _state = {'device': None, 'dtype': torch.bfloat16,
           'side_urgent_rows': int(os.environ.get('PASSL_SIDE_URGENT_ROWS', '500000') or 0),
           # the library's option wgrad_halo reads the same variable (csrc/options.h): 0 off, 1 images with sides % 8 == 0,
           # 2 all (default); hip/lib.py pushes this value into the library when it loads it
-          'wgrad_halo': int(os.environ.get('PASSL_WGRAD_HALO', '2') or 0)}
+          'wgrad_halo': int(os.environ.get('PASSL_WGRAD_HALO', '2') or 0),
+          # a BatchNorm's apply pass done on the operand of the 1x1 convolution that consumes it (nn.BNPending forward,
+          # nn.DyLink backward): bit masks over the K-tiles of that convolution's reduction, 1 = one (64 channels),
+          # 2 = two (128), 4 = three to seven.  Forward off: exact, but no gain inside the MoCo step
+          'igemm_a_bn': int(os.environ.get('PASSL_IGEMM_A_BN', '0') or 0) & 7,
+          'igemm_a_bnb': int(os.environ.get('PASSL_IGEMM_A_BNB', '7') or 0) & 7}
 
 
 def set_device(name):
@@ -165,9 +170,26 @@ def wgrad_halo():
     return _state['wgrad_halo']
 
 
+def igemm_a_bn(channels):
+    """Does a training-mode BatchNorm + ReLU over `channels` channels leave its apply pass to the 1x1 convolution that
+    is its only reader (flag igemm_a_bn, PASSL_IGEMM_A_BN: bit mask by K-tiles of 64 channels, default 0)?"""
+    return bool(_state['igemm_a_bn'] & _ktile_bit(channels))
+
+
+def igemm_a_bnb(channels):
+    """The same for the backward apply pass and the data-gradient launch of the convolution that feeds the BatchNorm
+    (flag igemm_a_bnb, PASSL_IGEMM_A_BNB, default 7)."""
+    return bool(_state['igemm_a_bnb'] & _ktile_bit(channels))
+
+
+def _ktile_bit(channels):
+    nk = (channels + 63) // 64
+    return 1 if nk == 1 else (2 if nk == 2 else 4)
+
+
 _BOOL_FLAGS = ('fused_bn_stats', 'fuse_residual_grad', 'fused_bn_backward', 'overlap', 'fork_downsample',
                'side_reductions', 'fused_stem_pool', 'fused_bn_backward2', 'stem_tail_flush', 'stem_wgrad_main_last')
-_INT_FLAGS = ('stem_wgrad_parts', 'side_urgent_rows', 'wgrad_halo')
+_INT_FLAGS = ('stem_wgrad_parts', 'side_urgent_rows', 'wgrad_halo', 'igemm_a_bn', 'igemm_a_bnb')
 
 
 def set_flag(name, value):

@@ -38,6 +38,10 @@ class ConvDesc(C.Structure):
                 ('bnb2_y', c_p), ('bnb2_mean', c_p), ('bnb2_invstd', c_p), ('bnb2_partial', c_p)]
 
 
+class ConvApro(C.Structure):
+    _fields_ = [('a2', c_p), ('a_scale', c_p), ('a_shift', c_p), ('a_coef', c_p), ('a_out', c_p), ('mode', C.c_int32)]
+
+
 class WgradDesc(C.Structure):
     _fields_ = [('a', c_p), ('dy', c_p), ('dw', c_p),
                 ('N', C.c_int32), ('OP', C.c_int32), ('OQ', C.c_int32), ('NCOLS', C.c_int32),
@@ -73,6 +77,7 @@ SIGNATURES = {
     'passl_hip_pack_weights': (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_p]),
     'passl_hip_nchw_to_nhwc_pad': (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
     'passl_hip_conv_igemm': (c_i, [C.POINTER(ConvDesc), c_p]),
+    'passl_hip_conv_igemm_apro': (c_i, [C.POINTER(ConvDesc), C.POINTER(ConvApro), c_p]),
     'passl_hip_conv_wgrad': (c_i, [C.POINTER(WgradDesc), c_p]),
     'passl_hip_slab_reduce': (c_i, [c_p, c_p, c_l, c_i, c_i, c_p]),
     'passl_hip_bn_partial_floats': (c_l, [c_i, c_i, c_i]),

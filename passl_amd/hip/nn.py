@@ -116,6 +116,63 @@ def bn_link(t):
     return getattr(t, '_passl_bn_link', None)
 
 
+class BNPending:
+    """The forward twin of BNLink: a training-mode BatchNorm + ReLU whose ONE consumer is a 1x1 convolution of the
+    register-staged kernel does not run its apply pass.  Its forward finalizes the statistics, allocates the output z and
+    lets this object ride on it: (y, scale, shift).  The consumer's forward launch reads y, applies the BatchNorm to the
+    operand on its way into the kernel and writes z (ops.conv_igemm(apro=...)) — one pass over the tensor less, one
+    launch less.  Until then z holds nothing: the tensor must reach that convolution and nothing else.  Where the library
+    does not serve the launch in that form, the consumer runs the apply pass itself, then the plain convolution."""
+
+    __slots__ = ('y', 'scale', 'shift')
+
+    def __init__(self, y, scale, shift):
+        self.y, self.scale, self.shift = y, scale, shift
+
+
+def bn_pending(t):
+    """The BNPending riding on a BatchNorm output tensor whose apply pass is still to be done (None otherwise)."""
+    return getattr(t, '_passl_bn_pending', None)
+
+
+class DyLink:
+    """BNPending's backward twin, between a convolution and the BatchNorm that reads its output.  When that BatchNorm's
+    output gradient arrives masked and reduced (BNLink.fused), its backward runs the finalize only, allocates dy and
+    `put`s (g, y, coef, dy) here; the convolution's data-gradient launch — the one reader of dy besides the weight
+    gradient — computes dy from g and y on its way in and writes it (ops.conv_igemm(apro=...)); the weight gradient,
+    launched after it, reads dy as before.  The link rides on the convolution's output tensor (dy_link) for the shapes
+    whose data gradient is one dense launch with a single 64-column block, and is used only by a BatchNorm that is told
+    it is that tensor's sole reader (_BatchNormBase.forward(sole_reader=True))."""
+
+    __slots__ = ('pending',)
+
+    def __init__(self):
+        self.pending = None
+
+    def put(self, g, y, coef, dy):
+        self.pending = (g, y, coef, dy)
+
+    def take(self, dy):
+        p, self.pending = self.pending, None
+        if p is not None and p[3].data_ptr() != dy.data_ptr():
+            raise RuntimeError('DyLink: the gradient that reached the convolution is not the one its BatchNorm deferred')
+        return p
+
+
+def dy_link(t):
+    """The DyLink riding on a convolution output tensor (None for anything else)."""
+    return getattr(t, '_passl_dy_link', None)
+
+
+def _apply_in_consumer(conv, y, residual, relu, stats):
+    """Shapes for which a BatchNorm leaves its apply pass to `conv` (include/passl_hip.h: passl_hip_conv_igemm_apro,
+    PASSL_APRO_BN_FWD) where config.igemm_a_bn allows it; the library has the last word (kernel selection)."""
+    g = conv.geom
+    return (relu and residual is None and stats is not None and y.dtype == torch.bfloat16 and not conv.is_stem and
+            g.k == 1 and g.stride == 1 and g.pad == 0 and g.cin == y.shape[-1] and g.cin % 64 == 0 and g.cin < 512 and
+            g.cout > 64 and config.igemm_a_bn(g.cin))
+
+
 class WgradLink:
     """Hand-off in the other direction, for the stem: the layer that PRODUCES a convolution's output gradient (the fused
     BatchNorm + ReLU + max-pool backward, two launches from the end of a backward pass) launches that convolution's
@@ -147,12 +204,22 @@ def _stem_wgrad_finish(layer, tmp):
 
 class _ConvFn(Function):
     @staticmethod
-    def forward(ctx, x, weight, layer, hw, stats, add_slot, sink_slot, producer, wlink=None):
+    def forward(ctx, x, weight, layer, hw, stats, add_slot, sink_slot, producer, wlink=None, pending=None,
+                dylink=None):
         rt = _need_rt(layer)
         N = x.shape[0]
         pl = layer._plan(N, hw[0], hw[1])
         y = torch.empty(N, pl.fd.OP, pl.fd.OQ, layer.geom.cout, dtype=x.dtype, device=x.device)
-        ops.conv_igemm(pl.fd, x, rt.w_fwd, y, stats=stats[0] if stats is not None else None)
+        slab = stats[0] if stats is not None else None
+        done = None
+        if pending is not None:
+            # x is the still-empty output of a BatchNorm (BNPending): this launch applies it and fills x
+            done = ops.conv_igemm(pl.fd, pending.y, rt.w_fwd, y, stats=slab,
+                                  apro=dict(mode=1, scale=pending.scale, shift=pending.shift, out=x))
+            if done is None:
+                ops.bn_apply(pending.y, pending.scale, pending.shift, None, True, out=x)
+        if done is None:
+            ops.conv_igemm(pl.fd, x, rt.w_fwd, y, stats=slab)
         if any(ctx.needs_input_grad):
             rt.arena.expect_grad(rt.indices)
         ctx.save_for_backward(x)
@@ -162,6 +229,7 @@ class _ConvFn(Function):
         # back-off of streams.enabled() flips in between
         ctx.side = streams.enabled(x)
         ctx.wlink = None
+        ctx.dylink = dylink
         if wlink is not None and ctx.side and any(ctx.needs_input_grad):
             # the producer of dy may launch the weight gradient in pieces of the batch (WgradLink)
             ctx.wlink = wlink
@@ -199,6 +267,11 @@ class _ConvFn(Function):
         streams.autograd_node_entry(dy.device)
         dy = dy.contiguous()
         dx = None
+        # dy may still be empty (DyLink): the data-gradient launch below fills it, or the apply pass does, here
+        late = ctx.dylink.take(dy) if ctx.dylink is not None else None
+        if late is not None and not (ctx.needs_input_grad[0] and len(pl.dds) == 1 and not pl.dgrad_zero):
+            ops.bn_bwd_apply_fused(late[0], late[1], late[2], dy)
+            late = None
         if ctx.needs_input_grad[0]:
             N = x.shape[0]
             alloc = ops.zeros if pl.dgrad_zero else torch.empty
@@ -232,6 +305,14 @@ class _ConvFn(Function):
                         bnb.update(y2=link.res_link.y, mean2=link.res_link.st[0], invstd2=link.res_link.st[1],
                                    partial2=slab2)
                     off += ops.conv_tiles(d)
+                if late is not None:
+                    done = ops.conv_igemm(d, late[0], rt.w_dgrad[id(d.pack)], dx, residual=extra, bnb=bnb,
+                                          apro=dict(mode=2, a2=late[1], coef=late[2], out=dy))
+                    if done is None:
+                        ops.bn_bwd_apply_fused(late[0], late[1], late[2], dy)
+                    late = None
+                    if done is not None:
+                        continue
                 ops.conv_igemm(d, dy, rt.w_dgrad[id(d.pack)], dx, residual=extra, bnb=bnb)
                 if slab2 is not None and not bnb.get('partial2_done', False):
                     slab2 = None          # the library took the launch without the second layer (ops.conv_igemm)
@@ -261,7 +342,7 @@ class _ConvFn(Function):
         else:
             wgrad()
         rt.arena.grad_ready(rt.indices)
-        return dx, None, None, None, None, None, None, None, None
+        return dx, None, None, None, None, None, None, None, None, None, None
 
 
 class Conv2D(Layer):
@@ -297,7 +378,7 @@ class Conv2D(Layer):
             self._plans[key] = pl
         return pl
 
-    def forward(self, x, hw=None, want_stats=False, add_slot=None, sink_slot=None, producer=None):
+    def forward(self, x, hw=None, want_stats=False, add_slot=None, sink_slot=None, producer=None, pending=None):
         """x: NHWC compute-dtype tensor (the stem takes the zero-padded image + hw=(H, W)).
         want_stats: also return the fused BatchNorm statistics slab written by the conv epilogue
         ((slab, tiles); None when the dtype has no fused path) -> (y, stats).
@@ -306,14 +387,21 @@ class Conv2D(Layer):
         returning it.
         producer: BNLink of the BatchNorm layer whose output is x, given ONLY when this conv's
         data-gradient launch produces the complete gradient of x (sole consumer, or the residual fork
-        folded in through add_slot): the launch then also does that BatchNorm's backward reduction."""
+        folded in through add_slot): the launch then also does that BatchNorm's backward reduction.
+        pending: BNPending of x when the BatchNorm that produced it left its apply pass to this conv (bn_pending(x))."""
         if hw is None:
             hw = (x.shape[1], x.shape[2])
         stats = None
         if want_stats and x.dtype == torch.bfloat16 and config.fused_bn_stats():
             stats = ops.conv_stats_buffer(self._plan(x.shape[0], hw[0], hw[1]).fd, x.device)
         wlink = WgradLink() if (self.is_stem and config.stem_wgrad_parts() > 1) else None
-        y = _ConvFn.apply(x, self.weight, self, hw, stats, add_slot, sink_slot, producer, wlink)
+        g = self.geom
+        dylink = DyLink() if (torch.is_grad_enabled() and x.dtype == torch.bfloat16 and not self.is_stem and
+                              g.k == 1 and g.stride == 1 and g.pad == 0 and g.cin <= 64 and g.cout % 64 == 0 and
+                              g.cout < 512 and config.fused_bn_backward() and config.igemm_a_bnb(g.cout)) else None
+        y = _ConvFn.apply(x, self.weight, self, hw, stats, add_slot, sink_slot, producer, wlink, pending, dylink)
+        if dylink is not None:
+            y._passl_dy_link = dylink
         if wlink is not None and wlink.launch is not None:
             y._passl_wgrad_link = wlink
         return (y, stats) if want_stats else y
@@ -351,14 +439,19 @@ def convert_sync_batchnorm(module):
 
 class _BNActFn(Function):
     @staticmethod
-    def forward(ctx, y, gamma, beta, residual, layer, relu, partial, res_slot, link_box, res_link=None):
+    def forward(ctx, y, gamma, beta, residual, layer, relu, partial, res_slot, link_box, res_link=None, pend_box=None,
+                dylink=None):
         has_res = residual is not None
         # SyncBatchNorm (convert_sync_batchnorm): statistics over every rank's batch when a process group is up
         ctx.sync = bool(getattr(layer, '_sync', False)) and _collectives_active()
         z, st, mask = ops.bn_train_fwd(y, gamma.detach(), beta.detach(), layer._mean,
                                        layer._variance, residual, relu, layer._momentum,
                                        layer._epsilon, partial=partial,
-                                       want_mask=relu and has_res, sync=ctx.sync)
+                                       want_mask=relu and has_res, sync=ctx.sync, apply=pend_box is None)
+        if pend_box is not None:
+            # statistics only: the consumer convolution applies them and fills z (BNPending)
+            z = torch.empty_like(y)
+            pend_box[0] = BNPending(y, st[2], st[3])
         # ReLU mask for the backward: recomputed from y (no residual) or the bit mask (residual):
         # the output z is never re-read by this layer's backward.
         ctx.relu_mode = 0 if not relu else (3 if has_res else 2)
@@ -367,6 +460,7 @@ class _BNActFn(Function):
         ctx.save_for_backward(y, st, mask)
         ctx.layer, ctx.has_res, ctx.res_slot = layer, has_res, res_slot
         ctx.link = None
+        ctx.dylink = dylink
         if link_box is not None:
             ctx.link = link_box[0] = BNLink(y, st, mask, ctx.relu_mode,
                                             res_link if (has_res and ctx.relu_mode == 3 and res_slot is None) else None)
@@ -393,15 +487,21 @@ class _BNActFn(Function):
             # the slab may have been written by a launch on ANOTHER stream (a downsample branch's layer runs its
             # backward on the side stream; its slab comes from the main stream's data-gradient launch and pool)
             fused[0].record_stream(torch.cuda.current_stream(dz.device))
-        dx, dres = ops.bn_bwd(dz.contiguous(), mask, y, gamma, st[0], st[1],
-                              dgamma, dbeta, relu=ctx.relu_mode,
-                              want_dres=want_dres, scale=st[2], shift=st[3], fused=fused, sync=ctx.sync)
+        dz = dz.contiguous()
+        # gradient already masked and reduced, and the convolution that produced y takes dx as a pending operand (DyLink)
+        defer = (fused is not None and ctx.dylink is not None and ctx.needs_input_grad[0] and
+                 dz.dtype == torch.bfloat16)
+        out = ops.bn_bwd(dz, mask, y, gamma, st[0], st[1], dgamma, dbeta, relu=ctx.relu_mode,
+                         want_dres=want_dres, scale=st[2], shift=st[3], fused=fused, sync=ctx.sync, defer=defer)
+        dx, dres = out[0], out[1]
+        if defer:
+            ctx.dylink.put(dz, y, out[2], dx)
         if ctx.res_slot is not None:
             ctx.res_slot.put(dres)
             dres = None
         if layer._rt is not None:
             layer._rt.arena.grad_ready(layer._rt.indices)
-        return dx, None, None, dres, None, None, None, None, None, None
+        return dx, None, None, dres, None, None, None, None, None, None, None, None
 
 
 class _BatchNormBase(Layer):
@@ -453,10 +553,15 @@ class _BatchNormBase(Layer):
             return self.weight.detach(), self.bias.detach()
         return self._const[0], self._const[1]
 
-    def forward(self, y, residual=None, relu=False, stats=None, res_slot=None, res_link=None):
+    def forward(self, y, residual=None, relu=False, stats=None, res_slot=None, res_link=None, consumer=None,
+                sole_reader=False):
         """stats: fused statistics from the producing conv's epilogue (Conv2D.forward(...,
         want_stats=True)); res_slot: GradSlot that receives the residual branch's gradient; res_link: bn_link of the
-        residual when it is the output of a BatchNorm that nothing else consumes (BNLink.res_link)."""
+        residual when it is the output of a BatchNorm that nothing else consumes (BNLink.res_link); consumer: the Conv2D
+        that is the ONLY reader of the output and is called with pending=bn_pending(output) (BNPending);
+        sole_reader: y is the output of a Conv2D and this layer is its ONLY reader, so this layer's backward may leave
+        its apply pass to that convolution's data-gradient launch (DyLink, riding on y).  Never set it for a tensor
+        that something else reads as well: autograd would add the still empty gradient to the other reader's."""
         if self.uses_global_stats():
             if torch.is_grad_enabled() and (y.requires_grad or (self.affine and self.weight.requires_grad)):
                 raise NotImplementedError('frozen BatchNorm inside a differentiated graph is not on '
@@ -467,9 +572,13 @@ class _BatchNormBase(Layer):
         box = [None] if (torch.is_grad_enabled() and y.dtype == torch.bfloat16 and
                          config.fused_bn_backward()) else None
         gamma, beta = (self.weight, self.bias) if self.affine else (self._const[0], self._const[1])
-        z = _BNActFn.apply(y, gamma, beta, residual, self, relu, stats, res_slot, box, res_link)
+        pend = [None] if (consumer is not None and _apply_in_consumer(consumer, y, residual, relu, stats)) else None
+        z = _BNActFn.apply(y, gamma, beta, residual, self, relu, stats, res_slot, box, res_link, pend,
+                           dy_link(y) if sole_reader else None)
         if box is not None and box[0] is not None:
             z._passl_bn_link = box[0]
+        if pend is not None:
+            z._passl_bn_pending = pend[0]
         return z
 
 

@@ -158,13 +158,18 @@ def conv_tiles(d: P.Desc):
 
 
 def conv_igemm(d: P.Desc, a, b, y, scale=None, shift=None, residual=None, relu=False,
-               out_f32=False, stats=None, bnb=None):
+               out_f32=False, stats=None, bnb=None, apro=None):
     """Launch one implicit-GEMM conv described by `d` (plan.Desc).  `a` activation tensor,
     `b` packed weights [NCOLS, R*S*C] (same dtype as a), `y` output tensor (written in place at
     d.y_off with d's strides).  `stats`: fp32 slab from conv_stats_buffer (fused forward BatchNorm
     statistics of the stored output, bf16 only).  `bnb`: dict(y, mask, mean, invstd, scale, shift,
     relu, partial, tile_off) — BatchNorm-backward statistics fused into this data-gradient launch
-    (include/passl_hip.h: passl_conv_desc.bnb_*)."""
+    (include/passl_hip.h: passl_conv_desc.bnb_*).
+    `apro`: dict(mode, out, scale, shift | a2, coef) — the apply pass of the BatchNorm whose output this launch consumes,
+    done on the A operand inside the launch (passl_hip_conv_igemm_apro): `a` is then that BatchNorm's INPUT (mode 1) or
+    its masked output gradient (mode 2, `a2` its input), and the transformed operand is also written to `out`.
+    Returns None, with nothing launched, when the library does not serve the launch in that form: the caller runs
+    the streaming pass and calls again without `apro`."""
     s = _conv_struct(d)
     esz = 4 if out_f32 else y.element_size()
     s.a = L.ptr(a)
@@ -198,6 +203,19 @@ def conv_igemm(d: P.Desc, a, b, y, scale=None, shift=None, residual=None, relu=F
         s.bnb_partial = None
         s.bnb_relu = s.bnb_tile_off = 0
         s.bnb2_y = s.bnb2_mean = s.bnb2_invstd = s.bnb2_partial = None
+    if apro is not None:
+        if d.y_off or bnb is not None and bnb.get('partial2') is not None:
+            return None
+        pro = L.ConvApro()
+        pro.mode = int(apro['mode'])
+        pro.a2, pro.a_coef = L.ptr(apro.get('a2')), L.ptr(apro.get('coef'))
+        pro.a_scale, pro.a_shift = L.ptr(apro.get('scale')), L.ptr(apro.get('shift'))
+        pro.a_out = L.ptr(apro['out'])
+        rc = _lib().passl_hip_conv_igemm_apro(C.byref(s), C.byref(pro), L.stream())
+        if rc == L.EUNSUPPORTED:
+            return None
+        L.check(rc, 'conv_igemm_apro')
+        return y
     rc = _lib().passl_hip_conv_igemm(C.byref(s), L.stream())
     if rc == L.EUNSUPPORTED and bnb is not None and bnb.get('partial2') is not None:
         # include/passl_hip.h (bnb2_*): the two-BatchNorm instantiations cover fewer launches than the Python-side test
@@ -331,11 +349,11 @@ def bn_train_fwd(x, gamma, beta, rmean, rvar, residual=None, relu=True, momentum
     return z, stats, mask
 
 
-def bn_apply(x, scale, shift, residual=None, relu=False):
-    """z = relu?(x*scale + shift + residual) with given per-channel affine (inference BN)."""
+def bn_apply(x, scale, shift, residual=None, relu=False, out=None):
+    """z = relu?(x*scale + shift + residual) with given per-channel affine (inference BN; `out`: write z there)."""
     Cch = x.shape[-1]
     M = x.numel() // Cch
-    z = torch.empty_like(x)
+    z = torch.empty_like(x) if out is None else out
     L.check(_lib().passl_hip_bn_apply(L.ptr(x), L.ptr(scale), L.ptr(shift), L.ptr(residual),
                                       L.ptr(z), None, M, Cch, 1 if relu else 0, L.dt(x),
                                       L.stream()), 'bn_apply')
@@ -343,13 +361,16 @@ def bn_apply(x, scale, shift, residual=None, relu=False):
 
 
 def bn_bwd(dz, z, x, gamma, mean, invstd, dgamma, dbeta, relu=True, want_dres=False,
-           scale=None, shift=None, fused=None, sync=False):
+           scale=None, shift=None, fused=None, sync=False, defer=False):
     """Returns dx (and dres).  dgamma/dbeta (fp32 [C]) are accumulated into.
     `relu`: False/0 none, True/1 mask = z > 0, 2 mask recomputed from x*scale+shift (z unused),
     3 `z` is the bit mask written by the forward's bn_apply.
     `fused` = (slab, tiles): the data-gradient launch that produced `dz` already masked it and wrote
     the (sum g, sum g*xhat) slab (conv_igemm(bnb=...)): no reduce pass, no mask in the apply pass,
-    and the residual-branch gradient IS dz (returned as dres without a copy)."""
+    and the residual-branch gradient IS dz (returned as dres without a copy).
+    `defer` (with `fused`): no apply pass either -> (dx, dres, coef) with dx allocated and EMPTY: the data-gradient
+    launch that consumes dx computes it from (dz, x, coef) on its way in and fills it (conv_igemm(apro=...)), or
+    the caller runs bn_bwd_apply_fused."""
     Cch = x.shape[-1]
     M = x.numel() // Cch
     dev = x.device
@@ -386,10 +407,20 @@ def bn_bwd(dz, z, x, gamma, mean, invstd, dgamma, dbeta, relu=True, want_dres=Fa
         dres_out, dres = None, (dz if want_dres else None)
     else:
         dres_out = dres = torch.empty_like(x) if want_dres else None
+    if defer and fused is not None:
+        return dx, dres, coef
     L.check(lib.passl_hip_bn_bwd_apply(L.ptr(dz), zp, L.ptr(x), L.ptr(coef), L.ptr(scale),
                                        L.ptr(shift), L.ptr(dx), L.ptr(dres_out), M, Cch, r, dtc, L.stream()),
             'bn_bwd_apply')
     return dx, dres
+
+
+def bn_bwd_apply_fused(g, x, coef, dx):
+    """The apply pass bn_bwd(defer=True) left out: dx = coef[0] * g + coef[1] * x + coef[2] (g already masked)."""
+    Cch = x.shape[-1]
+    L.check(_lib().passl_hip_bn_bwd_apply(L.ptr(g), None, L.ptr(x), L.ptr(coef), None, None, L.ptr(dx), None,
+                                          x.numel() // Cch, Cch, 0, L.dt(x), L.stream()), 'bn_bwd_apply')
+    return dx
 
 
 # ------------------------------------------------------------------ pooling / layout

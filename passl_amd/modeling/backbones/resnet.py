@@ -64,10 +64,12 @@ class BottleneckBlock(nn.Layer):
         x_ready = streams.record_event(torch.cuda.current_stream(x.device)) if fork else None
         out, st = self.conv1(x, want_stats=True, add_slot=slot,
                              producer=nn.bn_link(x) if slot is not None else None)
-        out = self.bn1(out, relu=True, stats=st)
+        # bn1, bn3 and the downsample BatchNorm are the only readers of their 1x1 convolutions' outputs (nn.DyLink)
+        out = self.bn1(out, relu=True, stats=st, sole_reader=True)
         out, st = self.conv2(out, want_stats=True, producer=nn.bn_link(out))
-        out = self.bn2(out, relu=True, stats=st)
-        out, st3 = self.conv3(out, want_stats=True, producer=nn.bn_link(out))
+        # bn2 + ReLU has one reader, a 1x1 convolution: that launch applies it to its operand (nn.BNPending)
+        out = self.bn2(out, relu=True, stats=st, consumer=self.conv3)
+        out, st3 = self.conv3(out, want_stats=True, producer=nn.bn_link(out), pending=nn.bn_pending(out))
         if self.downsample is not None:
             if fork:
                 main = torch.cuda.current_stream(x.device)
@@ -75,7 +77,7 @@ class BottleneckBlock(nn.Layer):
                 streams.wait_event(side, x_ready)
                 with torch.cuda.stream(side):
                     idn, st = self.downsample[0](x, want_stats=True, sink_slot=slot)
-                    identity = self.downsample[1](idn, relu=False, stats=st)
+                    identity = self.downsample[1](idn, relu=False, stats=st, sole_reader=True)
                 streams.wait_event(main, streams.record_event(side))
                 # `identity` comes from the side stream's pool and is read by bn3 on the main stream.  No
                 # record_stream (hip/streams.py, "Memory"): every later piece of side-stream work starts with
@@ -83,9 +85,10 @@ class BottleneckBlock(nn.Layer):
                 # reuse is already behind bn3
             else:
                 idn, st = self.downsample[0](x, want_stats=True, sink_slot=slot)
-                identity = self.downsample[1](idn, relu=False, stats=st)
-            return self.bn3(out, residual=identity, relu=True, stats=st3, res_link=nn.bn_link(identity))
-        return self.bn3(out, residual=x, relu=True, stats=st3, res_slot=slot)   # out += identity; relu
+                identity = self.downsample[1](idn, relu=False, stats=st, sole_reader=True)
+            return self.bn3(out, residual=identity, relu=True, stats=st3, res_link=nn.bn_link(identity),
+                            sole_reader=True)
+        return self.bn3(out, residual=x, relu=True, stats=st3, res_slot=slot, sole_reader=True)   # out += identity; relu
 
     def forward_frozen(self, x, allow_fork=True):
         """Same block with running-stat BN folded into the conv epilogues (3-4 kernels).  allow_fork=False: the

@@ -15,6 +15,7 @@
 //   tools/kbench finstress [iters=N]        ... and the multi-segment hand-off under load: every result bit-identical run to run
 //   tools/kbench poolcheck | pooltime       the stem's fused BatchNorm + ReLU + max-pool backward: second form == first form; times
 //   tools/kbench vtime                      the four epilogue variants of the K = 64 / 128 1x1 layers (igemm_lean=0 to compare)
+//   tools/kbench acheck | atime             passl_hip_conv_igemm_apro against bn_apply / bn_bwd_apply + conv_igemm: ==; us per launch
 //   tools/kbench ablate                     the register-staged kernel's debug switches on the 1x1 shapes
 //   tools/kbench sweep cfg [cfg ...]        cfg = "name=value,name=value": check + time the 3x3 shapes under each
 //   name=value pairs are passl_hip_set_option() calls made before anything runs.
@@ -29,6 +30,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <math.h>
+#include <functional>
 #include <string>
 #include <vector>
 #include "passl_hip.h"
@@ -930,6 +932,113 @@ static int run_ablate() {
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------------ A-operand prologue
+// acheck / atime: passl_hip_conv_igemm_apro (a BatchNorm's apply pass done on the A operand of a dense 1x1 launch, with
+// the transformed operand written back) against the two launches it replaces: passl_hip_bn_apply resp.
+// passl_hip_bn_bwd_apply, then passl_hip_conv_igemm on their output.  acheck: small ragged cases (M = 147), the
+// written-back operand, the convolution output and the statistics slab compared with ==.  atime: the ResNet-50 shapes
+// at N = 256: us of the streaming pass, of the plain launch, of the one launch, and what the one launch saves.
+struct AproCase { int mode, N, H, C, K; const char* note; };
+
+static float time_loop(int iters, const std::function<int()>& f) {
+  for (int i = 0; i < 3; ++i) if (f() != PASSL_OK) return -1.f;
+  hipEvent_t e0, e1;
+  CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+  CK(hipDeviceSynchronize());
+  CK(hipEventRecord(e0, 0));
+  for (int i = 0; i < iters; ++i) f();
+  CK(hipEventRecord(e1, 0));
+  CK(hipEventSynchronize(e1));
+  float ms = 0;
+  CK(hipEventElapsedTime(&ms, e0, e1));
+  CK(hipEventDestroy(e0)); CK(hipEventDestroy(e1));
+  return ms * 1000.f / iters;
+}
+
+static int run_apro(bool timing) {
+  static const AproCase kCheck[] = {
+      {PASSL_APRO_BN_FWD, 3, 7, 64, 256, "fwd  64->256 M=147 (lean)"}, {PASSL_APRO_BN_FWD, 3, 7, 128, 512, "fwd 128->512 M=147"},
+      {PASSL_APRO_BN_FWD, 3, 7, 256, 1024, "fwd 256->1024 M=147"},     {PASSL_APRO_BN_BWD, 3, 7, 64, 64, "bwd  64->64 M=147"},
+      {PASSL_APRO_BN_BWD, 3, 7, 256, 64, "bwd 256->64 M=147"}};
+  static const AproCase kTime[] = {
+      {PASSL_APRO_BN_FWD, 256, 56, 64, 256, "fwd  64->256 @56"},  {PASSL_APRO_BN_FWD, 256, 28, 128, 512, "fwd 128->512 @28"},
+      {PASSL_APRO_BN_FWD, 256, 14, 256, 1024, "fwd 256->1024 @14"}, {PASSL_APRO_BN_BWD, 256, 56, 256, 64, "bwd 256->64 @56"},
+      {PASSL_APRO_BN_BWD, 256, 56, 64, 64, "bwd  64->64 @56"}};
+  const AproCase* cases = timing ? kTime : kCheck;
+  const int ncases = 5;
+  if (timing) printf("%-26s %10s %10s %10s %10s\n", "launch (N=256, +stats fwd)", "bn pass us", "conv us", "one us", "saved us");
+  int failed = 0;
+  for (int ci = 0; ci < ncases; ++ci) {
+    const AproCase& c = cases[ci];
+    const bool fwd = c.mode == PASSL_APRO_BN_FWD;
+    const Shape s = {c.N, c.C, c.K, 1, 1, c.H, c.note, 1};
+    const int64_t M = (int64_t)c.N * c.H * c.H, na = M * c.C, nb = (int64_t)c.K * c.C, ny = M * c.K;
+    const int tiles = (int)((M + 127) / 128);
+    void *a = nullptr, *a2 = nullptr, *b = nullptr, *z0 = nullptr, *z1 = nullptr, *y0 = nullptr, *y1 = nullptr;
+    float *st0 = nullptr, *st1 = nullptr, *cols = nullptr;
+    CK(hipMalloc(&a, na * 2)); CK(hipMalloc(&a2, na * 2)); CK(hipMalloc(&b, nb * 2));
+    CK(hipMalloc(&z0, na * 2)); CK(hipMalloc(&z1, na * 2)); CK(hipMalloc(&y0, ny * 2)); CK(hipMalloc(&y1, ny * 2));
+    CK(hipMalloc((void**)&st0, (int64_t)tiles * c.K * 12)); CK(hipMalloc((void**)&st1, (int64_t)tiles * c.K * 12));
+    CK(hipMalloc((void**)&cols, 3 * c.C * 4));
+    fill(a, na, 11u); fill(a2, na, 37u); fill(b, nb, 23u);
+    std::vector<float> h(3 * c.C);
+    for (int k = 0; k < c.C; ++k) {
+      h[k] = (mix((uint64_t)k, 47u) & 1u) ? 1.25f : -0.5f;                  // scale / cA
+      h[c.C + k] = (float)ival((uint64_t)k, 53u) * 0.0625f;                  // shift / cB
+      h[2 * c.C + k] = (float)ival((uint64_t)k, 59u) * 0.03125f;             // cC
+    }
+    CK(hipMemcpy(cols, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+    CK(hipMemset(z0, 0xff, na * 2)); CK(hipMemset(z1, 0xff, na * 2));
+    CK(hipMemset(y0, 0xff, ny * 2)); CK(hipMemset(y1, 0xff, ny * 2));
+    CK(hipMemset(st0, 0xff, (int64_t)tiles * c.K * 12)); CK(hipMemset(st1, 0xff, (int64_t)tiles * c.K * 12));
+    passl_conv_desc d0 = make_desc(s, z0, b, y0), d1 = make_desc(s, a, b, y1);
+    if (fwd) { d0.stats = st0; d1.stats = st1; d0.stats_tiles = d1.stats_tiles = tiles; }
+    passl_conv_apro pro;
+    memset(&pro, 0, sizeof(pro));
+    pro.mode = c.mode; pro.a_out = z1;
+    if (fwd) { pro.a_scale = cols; pro.a_shift = cols + c.C; } else { pro.a2 = a2; pro.a_coef = cols; }
+    auto pass = [&]() {
+      return fwd ? passl_hip_bn_apply(a, cols, cols + c.C, nullptr, z0, nullptr, M, c.C, 1, PASSL_BF16, nullptr)
+                 : passl_hip_bn_bwd_apply(a, nullptr, a2, cols, nullptr, nullptr, z0, nullptr, M, c.C, 0, PASSL_BF16, nullptr);
+    };
+    auto conv = [&]() { return passl_hip_conv_igemm(&d0, nullptr); };
+    auto one = [&]() { return passl_hip_conv_igemm_apro(&d1, &pro, nullptr); };
+    if (timing) {
+      const float tp = time_loop(20, pass), tc = time_loop(20, conv), to = time_loop(20, one);
+      if (tp < 0 || tc < 0 || to < 0) { printf("%-26s refused\n", c.note); ++failed; }
+      else printf("%-26s %10.1f %10.1f %10.1f %10.1f\n", c.note, tp, tc, to, tp + tc - to);
+    } else {
+      int rc = pass();
+      if (rc == PASSL_OK) rc = conv();
+      const int rc1 = one();
+      CK(hipDeviceSynchronize());
+      if (rc != PASSL_OK || rc1 != PASSL_OK) { printf("%-26s separate -> %d, one launch -> %d\n", c.note, rc, rc1); ++failed; }
+      else {
+        std::vector<uint16_t> h0(na > ny ? na : ny), h1(h0.size());
+        std::vector<float> s0((size_t)tiles * c.K * 3), s1(s0.size());
+        CK(hipMemcpy(h0.data(), z0, na * 2, hipMemcpyDeviceToHost)); CK(hipMemcpy(h1.data(), z1, na * 2, hipMemcpyDeviceToHost));
+        const bool zok = memcmp(h0.data(), h1.data(), na * 2) == 0;
+        int64_t zeros = 0;
+        for (int64_t i = 0; i < na; ++i) zeros += (h0[i] & 0x7fffu) == 0;
+        CK(hipMemcpy(h0.data(), y0, ny * 2, hipMemcpyDeviceToHost)); CK(hipMemcpy(h1.data(), y1, ny * 2, hipMemcpyDeviceToHost));
+        const bool yok = memcmp(h0.data(), h1.data(), ny * 2) == 0;
+        bool sok = true;
+        if (fwd) {
+          CK(hipMemcpy(s0.data(), st0, s0.size() * 4, hipMemcpyDeviceToHost)); CK(hipMemcpy(s1.data(), st1, s1.size() * 4, hipMemcpyDeviceToHost));
+          sok = memcmp(s0.data(), s1.data(), s0.size() * 4) == 0;
+        }
+        printf("%-26s operand %s  output %s  statistics %s  (%.0f %% of the operand is zero)\n", c.note, zok ? "==" : "DIFFERS",
+               yok ? "==" : "DIFFERS", fwd ? (sok ? "==" : "DIFFERS") : "-", 100.0 * zeros / na);
+        if (!zok || !yok || !sok) ++failed;
+      }
+    }
+    CK(hipFree(a)); CK(hipFree(a2)); CK(hipFree(b)); CK(hipFree(z0)); CK(hipFree(z1)); CK(hipFree(y0)); CK(hipFree(y1));
+    CK(hipFree(st0)); CK(hipFree(st1)); CK(hipFree(cols));
+  }
+  if (!timing) printf(failed ? "acheck: %d case(s) FAILED\n" : "acheck: all cases exact\n", failed);
+  return failed ? 1 : 0;
+}
+
 int main(int argc, char** argv) {
   if (passl_hip_abi_version() != PASSL_HIP_ABI_VERSION) {
     fprintf(stderr, "kbench was built against ABI %d of include/passl_hip.h, libpassl_hip.so is ABI %d: run tools/build_kbench.sh\n",
@@ -959,6 +1068,8 @@ int main(int argc, char** argv) {
   }
   printf("libpassl_hip ABI %d\n", passl_hip_abi_version());
   if (mode == "check") return run_check();
+  if (mode == "acheck") return run_apro(false);
+  if (mode == "atime") return run_apro(true);
   if (mode == "ablate") return run_ablate();
   if (mode == "vtime") return run_vtime();
   if (mode == "wcheck") return run_wcheck();
