@@ -775,6 +775,56 @@ int passl_hip_random_erase(const float* x, float* out, const int32_t* boxes, int
 int passl_hip_crop_resize_norm(const uint8_t* src, float* out, const int32_t* table, int B, int Hs, int Ws, int S,
                                const float* mean_std_scale, passl_stream_t stream);
 
+/* The same crop and resampling (the same device code path up to the vertical pass), ending in the resized image itself:
+ * out uint8 [B][S][S][3] (HWC), flipped left-right when flip != 0; no normalisation.  The input of the colour stage below.
+ * Same envelope and argument checks (out needs no alignment). */
+int passl_hip_crop_resize_u8(const uint8_t* src, uint8_t* out, const int32_t* table, int B, int Hs, int Ws, int S,
+                             passl_stream_t stream);
+
+/* ---------------------------------------------------------------- colour jitter, grayscale, solarise, Gaussian blur
+ * Reference: ColorJitter, RandomGrayscale, SimCLRGaussianBlur, BYOLSolarize of passl/data/preprocess/basic_transforms.py
+ * (:770-787, :872-944), which run on the host through Pillow, sample by sample.  img uint8 [B][H][W][3] (HWC, never
+ * written).  table: a DEVICE table int32 [B][24], one row per sample:
+ *   [0] n, the number of operations (<= 8)   [1] flip   [2] blur r (< 0: the sample is not blurred)   [3] ww   [4] fw
+ *   [5] split: operations [0, split) run before the blur, [split, n) after it (split = n without a blur)
+ *   [6] the index of the sample's contrast entry (< 0: none; at most one, before split)   [7] 0
+ *   [8..16) codes: 0 none, 1 brightness, 2 contrast, 3 saturation, 4 hue, 5 grayscale, 6 solarise
+ *   [16..24) values: the bits of the fp32 factor (1, 2, 3), the hue shift in [0, 256) (4), unused otherwise
+ * RESULT, Pillow's 8-bit arithmetic bit for bit:
+ *   blend(deg, v, a) = float(deg) + a * float(v - deg), the product and the sum each rounded to fp32 (no fused
+ *     multiply-add); for 0 <= a <= 1 truncated to uint8, otherwise 0 for t <= 0, 255 for t >= 255, truncated in between
+ *   gray = (19595 R + 38470 G + 7471 B + 0x8000) >> 16
+ *   brightness: blend(0, v, a); saturation: blend(gray, v, a); contrast: blend(m, v, a), m = (2 sums[b] + H W) / (2 H W);
+ *   hue: RGB -> HSV, H = (H + shift) mod 256, HSV -> RGB, as Pillow's Convert.c (csrc/view_aug_pixel.h);
+ *   grayscale: R = G = B = gray; solarise: v < 128 ? v : 255 - v.
+ * The library cannot read the table on the host: the caller validates it; the kernels clamp every count, index and radius
+ * and treat an unknown code as "none", so no access leaves a tensor whatever the table holds.  Common argument errors:
+ * NULL pointers, B < 0, H, W <= 0, a sample of 2^31 bytes or more, a table not 4-byte aligned -> PASSL_EINVAL; B == 0 ->
+ * PASSL_OK, nothing launched.
+ *
+ * view_gray_sum: sums[b] (8-byte aligned, [B]) = the sum of gray over sample b after its operations [0, contrast index),
+ *   0 for a sample without a contrast entry.  Integer sums, one workgroup per sample: exact and order-free, no atomics. */
+int passl_hip_view_gray_sum(const uint8_t* img, const int32_t* table, uint64_t* sums, int B, int H, int W,
+                            passl_stream_t stream);
+/* view_pointwise: the operations of one part of every sample's list: part 0 = [0, n), 1 = [0, split), 2 = [split, n).
+ *   Exactly one output: out_u8 uint8 [B][H][W][3] (the flip is NOT applied), or out_f32 fp32 [B][3][H][W], flipped
+ *   left-right when flip != 0 and normalised, (float(v) * scale - mean[c]) / std[c] as passl_hip_crop_resize_norm does
+ *   (mean_std_scale: 7 HOST floats; 16-byte stores when W % 4 == 0 and out_f32 is 16-byte aligned, single floats
+ *   otherwise).  sums: what view_gray_sum wrote, or NULL when no sample has a contrast entry. */
+int passl_hip_view_pointwise(const uint8_t* img, const int32_t* table, const uint64_t* sums, uint8_t* out_u8,
+                             float* out_f32, int B, int H, int W, int part, const float* mean_std_scale,
+                             passl_stream_t stream);
+/* gaussian_blur_u8: Pillow's ImageFilter.GaussianBlur = three box passes along x, then three along y, each rounding to
+ *   uint8, every tap clamped to the image at every pass:
+ *     out[x] = (ww sum_{|k| <= r} p[x + k] + fw (p[x - r - 1] + p[x + r + 1]) + 2^23) >> 24     (32-bit unsigned)
+ *   (r, ww, fw) per sample from the table, computed by the host (fp32: s2 = radius^2 / 3, L = sqrt(12 s2 + 1),
+ *   l = floor((L - 1) / 2), fr = l + (2l + 1)(l(l + 1) - 3 s2) / (6 (s2 - (l + 1)^2)), r = (int)fr,
+ *   ww = (uint32)(2^24 / (2 fr + 1)), fw = (2^24 - (2r + 1) ww) / 2).  Out of place (img == out -> PASSL_EINVAL); samples
+ *   with r < 0 are copied.  r_max: the largest r of the table, as the caller knows it; above the built maximum (1, which
+ *   covers a radius up to about 2.3) -> PASSL_EUNSUPPORTED.  The kernel clamps r to the built maximum. */
+int passl_hip_gaussian_blur_u8(const uint8_t* img, uint8_t* out, const int32_t* table, int B, int H, int W, int r_max,
+                               passl_stream_t stream);
+
 /* ---------------------------------------------------------------- measurement hooks */
 
 /* When enabled, every passl_hip_conv_igemm / passl_hip_conv_wgrad launch is bracketed by HIP

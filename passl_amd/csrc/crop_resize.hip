@@ -38,6 +38,9 @@
 // (top, left into it, then 1 <= h <= Hs - top, 1 <= w <= Ws - left), and every LDS index to its carve, so no access
 // leaves a tensor whatever the table holds.  Nothing here assumes that the crop is the whole resampled source: an
 // output window (Resize + CenterCrop) would add an offset to `i` in axis_coeffs.
+//
+// passl_hip_crop_resize_u8 is the same crop and resample ending in the uint8 HWC image (crop_resize_u8_kernel): the input
+// of the colour stage of view_aug.hip.
 #include "common.h"
 
 #pragma clang fp contract(off)
@@ -197,6 +200,88 @@ __global__ void __launch_bounds__(kThreads) crop_resize_norm_kernel(const uint8_
   }
 }
 
+// The same band, ending in the resized uint8 HWC image (flipped when the table says so) instead of flip + normalise +
+// fp32 NCHW: coefficients, carve, clamps and both passes as above, no normalisation table.  (A body shared by both
+// kernels through an inlined template changed the register allocation of crop_resize_norm_kernel, so the band loop is
+// written twice and axis_coeffs / carve / clip8 / crop_geom are what the two share.)
+__global__ void __launch_bounds__(kThreads) crop_resize_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ out,
+                                                                  const int32_t* __restrict__ table, CropGeom g) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const Carve cv = carve(g);
+  int32_t* hk = reinterpret_cast<int32_t*>(smem + cv.hk);
+  int32_t* hlo = reinterpret_cast<int32_t*>(smem + cv.hlo);
+  int32_t* hcnt = reinterpret_cast<int32_t*>(smem + cv.hcnt);
+  int32_t* vk = reinterpret_cast<int32_t*>(smem + cv.vk);
+  int32_t* vlo = reinterpret_cast<int32_t*>(smem + cv.vlo);
+  int32_t* vcnt = reinterpret_cast<int32_t*>(smem + cv.vcnt);
+  uint8_t* rows = reinterpret_cast<uint8_t*>(smem + cv.rows);
+
+  const int tid = threadIdx.x;
+  const int S = g.S;
+  const int b = blockIdx.x / g.bands;                        // uniform over the workgroup
+  const int y0 = (blockIdx.x - b * g.bands) * kBand;
+  const int ny = min(kBand, S - y0);
+  // the box, clamped to the source: 0 <= top < Hs, 1 <= h <= Hs - top, likewise left / w, whatever the table holds
+  const int32_t* t = table + (int64_t)b * 8;
+  const int top = min(max(t[0], 0), g.Hs - 1), left = min(max(t[1], 0), g.Ws - 1);
+  const int h = min(max(t[2], 1), g.Hs - top), w = min(max(t[3], 1), g.Ws - left);
+  const bool flip = t[4] != 0;
+
+  for (int i = tid; i < S; i += kThreads) axis_coeffs(w, S, i, g.KH, hk + i * g.KH, hlo[i], hcnt[i]);
+  if (tid >= kThreads - kBand) {                             // (the last lanes: the first ones carry a second column at S > 240)
+    const int i = tid - (kThreads - kBand);
+    if (i < ny) axis_coeffs(h, S, y0 + i, g.KV, vk + i * g.KV, vlo[i], vcnt[i]);
+  }
+  __syncthreads();
+
+  // the crop rows [row_lo, row_lo + nr) feed this band (lo and lo + cnt do not decrease with the output row)
+  const int row_lo = vlo[0];
+  const int nr = min(vlo[ny - 1] + vcnt[ny - 1] - row_lo, g.NR);
+  const uint8_t* crop = src + (((int64_t)b * g.Hs + top + row_lo) * g.Ws + left) * 3;
+  const int per_row = 3 * S;
+  for (int i = tid; i < nr * per_row; i += kThreads) {
+    const int r = i / per_row;
+    const int rem = i - r * per_row;
+    const int x = rem / 3, c = rem - x * 3;
+    const uint8_t* p = crop + ((int64_t)r * g.Ws + hlo[x]) * 3 + c;
+    const int32_t* K = hk + x * g.KH;
+    const int n = hcnt[x];
+    int acc = 1 << (kPrec - 1);
+    for (int k = 0; k < n; ++k) acc += K[k] * (int)p[3 * k];
+    rows[(r * 3 + c) * S + x] = (uint8_t)clip8(acc);
+  }
+  __syncthreads();
+
+  uint8_t* image = out + ((int64_t)b * S + y0) * S * 3;
+  for (int i = tid; i < ny * per_row; i += kThreads) {
+    const int y = i / per_row;
+    const int rem = i - y * per_row;
+    const int x = rem / 3, c = rem - x * 3;
+    const int32_t* K = vk + y * g.KV;
+    const int n = vcnt[y];
+    const int base = vlo[y] - row_lo;
+    const int xs = flip ? S - 1 - x : x;
+    int acc = 1 << (kPrec - 1);
+    for (int k = 0; k < n; ++k) acc += K[k] * (int)rows[(max(min(base + k, nr - 1), 0) * 3 + c) * S + xs];
+    image[i] = (uint8_t)clip8(acc);
+  }
+}
+
+// the launch geometry of both entry points; PASSL_OK, or the status to return
+int crop_geom(int B, int Hs, int Ws, int S, CropGeom& g, Carve& cv) {
+  // the carve's capacities, from the SOURCE extent: a crop is never larger.  ceil() of the exact rationals, in integers.
+  auto ceil_div = [](int64_t a, int64_t b) { return (a + b - 1) / b; };
+  const int64_t sup_h = Hs > S ? ceil_div(2ll * Hs, S) : 2, sup_w = Ws > S ? ceil_div(2ll * Ws, S) : 2;
+  const int64_t KH = 2 * sup_w + 1, KV = 2 * sup_h + 1;
+  const int64_t NR = (Hs > S ? ceil_div((int64_t)(kBand - 1) * Hs, S) : kBand - 1) + 2 * sup_h + 3;
+  const int64_t bands = ceil_div(S, kBand);
+  const int64_t lds = 4ll * S * (KH + 2) + 4ll * kBand * (KV + 2) + 3072 + 3ll * S * NR + 8 * 16;
+  if (lds > kLdsMax || bands * B > 0x7fffffffll) return PASSL_EUNSUPPORTED;
+  g.Hs = Hs; g.Ws = Ws; g.S = S; g.KH = (int)KH; g.KV = (int)KV; g.NR = (int)NR; g.bands = (int)bands;
+  cv = carve(g);
+  return cv.total > kLdsMax ? PASSL_EUNSUPPORTED : PASSL_OK;
+}
+
 }  // namespace
 
 extern "C" int passl_hip_crop_resize_norm(const uint8_t* src, float* out, const int32_t* table, int B, int Hs, int Ws,
@@ -207,30 +292,38 @@ extern "C" int passl_hip_crop_resize_norm(const uint8_t* src, float* out, const 
   for (int c = 0; c < 3; ++c)
     if (!(mean_std_scale[3 + c] != 0.0f)) return PASSL_EINVAL;      // (a zero or NaN std)
   if (B == 0) return PASSL_OK;
-  // the carve's capacities, from the SOURCE extent: a crop is never larger.  ceil() of the exact rationals, in integers.
-  auto ceil_div = [](int64_t a, int64_t b) { return (a + b - 1) / b; };
-  const int64_t sup_h = Hs > S ? ceil_div(2ll * Hs, S) : 2, sup_w = Ws > S ? ceil_div(2ll * Ws, S) : 2;
-  const int64_t KH = 2 * sup_w + 1, KV = 2 * sup_h + 1;
-  const int64_t NR = (Hs > S ? ceil_div((int64_t)(kBand - 1) * Hs, S) : kBand - 1) + 2 * sup_h + 3;
-  const int64_t bands = ceil_div(S, kBand);
-  const int64_t lds = 4ll * S * (KH + 2) + 4ll * kBand * (KV + 2) + 3072 + 3ll * S * NR + 8 * 16;
-  if (lds > kLdsMax || bands * B > 0x7fffffffll) return PASSL_EUNSUPPORTED;
   CropGeom g;
-  g.Hs = Hs; g.Ws = Ws; g.S = S; g.KH = (int)KH; g.KV = (int)KV; g.NR = (int)NR; g.bands = (int)bands;
+  Carve cv;
+  if (const int rc = crop_geom(B, Hs, Ws, S, g, cv)) return rc;
   for (int c = 0; c < 3; ++c) {
     g.mean[c] = mean_std_scale[c];
     g.stdv[c] = mean_std_scale[3 + c];
   }
   g.scale = mean_std_scale[6];
-  const Carve cv = carve(g);
-  if (cv.total > kLdsMax) return PASSL_EUNSUPPORTED;
-  const dim3 grid((unsigned)(bands * B));
+  const dim3 grid((unsigned)(g.bands * B));
   if ((S & 3) == 0 && aligned16(out))
     hipLaunchKernelGGL((crop_resize_norm_kernel<4>), grid, dim3(kThreads), (size_t)cv.total, as_stream(stream), src, out,
                        table, g);
   else
     hipLaunchKernelGGL((crop_resize_norm_kernel<1>), grid, dim3(kThreads), (size_t)cv.total, as_stream(stream), src, out,
                        table, g);
+  PASSL_RETURN_IF_LAUNCH_FAILED();
+  return PASSL_OK;
+}
+
+extern "C" int passl_hip_crop_resize_u8(const uint8_t* src, uint8_t* out, const int32_t* table, int B, int Hs, int Ws, int S,
+                                        passl_stream_t stream) {
+  if (!src || !out || !table || B < 0 || Hs <= 0 || Ws <= 0 || S <= 0) return PASSL_EINVAL;
+  if (reinterpret_cast<uintptr_t>(table) & 3u) return PASSL_EINVAL;
+  if ((int64_t)Hs * Ws * 3 >= (1ll << 31) || (int64_t)S * S * 3 >= (1ll << 31)) return PASSL_EINVAL;
+  if (B == 0) return PASSL_OK;
+  CropGeom g;
+  Carve cv;
+  if (const int rc = crop_geom(B, Hs, Ws, S, g, cv)) return rc;
+  for (int c = 0; c < 3; ++c) g.mean[c] = 0.0f, g.stdv[c] = 1.0f;
+  g.scale = 1.0f;
+  hipLaunchKernelGGL(crop_resize_u8_kernel, dim3((unsigned)(g.bands * B)), dim3(kThreads), (size_t)cv.total,
+                     as_stream(stream), src, out, table, g);
   PASSL_RETURN_IF_LAUNCH_FAILED();
   return PASSL_OK;
 }

@@ -21,10 +21,12 @@ def build_dataloader(cfg, device):
     becomes the loader's ``batch_transform``: erasing happens in the loader, i.e. before ``mixup_fn`` — the reference's
     order, per-sample transform first, then the collate-time mix.  Every other entry stays ignored there.
     A SyntheticRawLabeled source (uint8 HWC images) honours its whole ``transforms`` list: crop, flip, NormalizeImage and
-    ToCHWImage become one preprocess.DeviceCropPipeline, followed by the eraser when the list ends in ``RandomErasing``."""
+    ToCHWImage become one preprocess.DeviceCropPipeline, followed by the eraser when the list ends in ``RandomErasing``.
+    A SyntheticRawTwoView source honours its ``transform`` block (the v2 schema's key; ``transforms`` is read too): one
+    TwoViewsTransform of two view pipelines (preprocess.view_aug), so the loader yields (x_q, x_k) of the same images."""
     from .preprocess import build_mixup, build_random_erasing
     from .preprocess.crop import ChainedBatchTransform, build_crop_pipeline
-    from .synthetic import SyntheticLabeled, SyntheticLoader, SyntheticRawLabeled
+    from .synthetic import SyntheticLabeled, SyntheticLoader, SyntheticRawLabeled, SyntheticRawTwoView
     ds_cfg = dict(cfg['dataset'])
     mixup_cfg = ds_cfg.pop('batch_transforms', None)
     sampler = cfg.get('sampler', {})
@@ -33,6 +35,9 @@ def build_dataloader(cfg, device):
     if isinstance(dataset, SyntheticRawLabeled):
         crop = build_crop_pipeline(ds_cfg.get('transforms', None))
         eraser = crop if eraser is None else ChainedBatchTransform([crop, eraser])
+    if isinstance(dataset, SyntheticRawTwoView):
+        from .preprocess.view_aug import build_two_views
+        eraser = build_two_views(ds_cfg.get('transform', None) or ds_cfg.get('transforms', None))
     loader = SyntheticLoader(dataset, batch_size=sampler.get('batch_size', 32), device=device,
                              drop_last=sampler.get('drop_last', True), batch_transform=eraser)
     ring = int((cfg.get('loader', None) or {}).get('host_ring', 0) or 0)

@@ -102,6 +102,29 @@ class SyntheticRawLabeled(SyntheticLabeled):
 
 
 @DATASETS.register()
+class SyntheticRawTwoView(object):
+    """Unlabeled images as a decoder hands them out: uint8 [source_h, source_w, 3] (HWC), N(128, 48^2) rounded and cut
+    to [0, 255], SyntheticRawLabeled's images without the labels and their colour cast.  The ``transform`` block of its
+    config, ``[{TwoViewsTransform: {base_transform1: [...], base_transform2: [...]}}]``, is honoured entry by entry
+    (build_dataloader): crop, colour jitter, grayscale, blur, solarise, flip, NormalizeImage and ToCHWImage run on the
+    resident batch (preprocess.TwoViewsTransform), so a step receives (x_q, x_k), two fp32 [3, S, S] views of the SAME
+    image, like SyntheticTwoView's independent ones."""
+
+    def __init__(self, num_samples=1281167, source_h=256, source_w=256, image_size=224, seed=1234, num_batches_cached=1,
+                 **ignored):
+        self.num_samples, self.image_size = int(num_samples), int(image_size)
+        self.source_h, self.source_w = int(source_h), int(source_w)
+        self.seed, self.num_batches_cached = int(seed), int(num_batches_cached)
+
+    def __len__(self):
+        return self.num_samples
+
+    def make_batch(self, gen, batch_size):
+        image = torch.randn(batch_size, self.source_h, self.source_w, 3, generator=gen) * 48. + 128.
+        return (image.round().clamp(0, 255).to(torch.uint8),)
+
+
+@DATASETS.register()
 class ImageNet(object):
     def __init__(self, **kwargs):
         raise NotImplementedError(
@@ -179,7 +202,8 @@ class SyntheticLoader(object):
             if self._tail and i == n - 1 and self._len > 0:
                 b = tuple(t[:self._tail] for t in b)
             if self.batch_transform is not None:
-                b = (self.batch_transform(b[0]),) + tuple(b[1:])
+                out = self.batch_transform(b[0])             # (a TwoViewsTransform hands out two tensors)
+                b = (out if isinstance(out, tuple) else (out,)) + tuple(b[1:])
             yield b
 
 
@@ -264,7 +288,8 @@ class HostRingLoader(object):
     def _transformed(self, b):
         if self.batch_transform is None:
             return b
-        return (self.batch_transform(b[0]),) + tuple(b[1:])          # out of place, on the compute stream
+        out = self.batch_transform(b[0])                             # out of place, on the compute stream
+        return (out if isinstance(out, tuple) else (out,)) + tuple(b[1:])
 
     def __iter__(self):
         for _ in range(len(self)):

@@ -168,6 +168,10 @@ SIGNATURES = {
     'passl_hip_soft_ce_bwd': (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p]),
     'passl_hip_random_erase': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_l, c_l, c_p]),
     'passl_hip_crop_resize_norm': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p]),
+    'passl_hip_crop_resize_u8': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
+    'passl_hip_view_gray_sum': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
+    'passl_hip_view_pointwise': (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p]),
+    'passl_hip_gaussian_blur_u8': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
     'passl_hip_adamw': (c_i, [c_p, c_p, c_p, c_p, c_l, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_p]),
     'passl_hip_adamw_dev': (c_i, [c_p, c_p, c_p, c_p, c_l, c_p, c_f, c_f, c_f, c_f, c_f, c_p]),
     'passl_hip_adamw_groups_dev': (c_i, [c_p, c_p, c_p, c_p, c_l, c_p, c_p, c_p, c_i, c_p, c_f, c_f, c_f, c_f, c_p]),

@@ -932,6 +932,86 @@ def crop_resize_norm(src, table, size, mean, std, scale):
     return out
 
 
+def crop_resize_u8(src, table, size):
+    """The same crop and bicubic resample, ending in the resized image: a new uint8 [B,size,size,3] (HWC), flipped
+    where the table's flip is set — the input of the colour stage below."""
+    assert src.dtype == torch.uint8 and src.dim() == 4 and src.shape[3] == 3 and src.is_contiguous()
+    assert table.dtype == torch.int32 and table.is_contiguous() and tuple(table.shape) == (src.shape[0], 8)
+    B, Hs, Ws, _ = src.shape
+    size = int(size)
+    out = torch.empty(B, size, size, 3, dtype=torch.uint8, device=src.device)
+    if B == 0 and src.is_cuda:
+        return out
+    L.check(_lib().passl_hip_crop_resize_u8(L.ptr(src), L.ptr(out), L.ptr(table), B, Hs, Ws, size, L.stream()),
+            'crop_resize_u8')
+    return out
+
+
+# ------------------------------------------------------------------ colour jitter, grayscale, solarise, blur (csrc/view_aug.hip)
+VIEW_ROW = 24                                             # int32 per row of the operation table (include/passl_hip.h)
+BLUR_R_MAX = 1                                            # the box radius the blur kernel is built for
+
+
+def _view_args(img, table):
+    assert img.dtype == torch.uint8 and img.dim() == 4 and img.shape[3] == 3 and img.is_contiguous()
+    assert table.dtype == torch.int32 and table.is_contiguous() and tuple(table.shape) == (img.shape[0], VIEW_ROW)
+    return img.shape[0], img.shape[1], img.shape[2]
+
+
+def view_gray_sum(img, table):
+    """img uint8 [B,H,W,3]; table int32 [B,24] on the device -> int64 [B]: per sample the sum of gray over the image after
+    the operations that precede its contrast entry (0 without one).  Exact integer sums."""
+    B, H, W = _view_args(img, table)
+    sums = torch.empty(B, dtype=torch.int64, device=img.device)
+    if B:
+        L.check(_lib().passl_hip_view_gray_sum(L.ptr(img), L.ptr(table), L.ptr(sums), B, H, W, L.stream()),
+                'view_gray_sum')
+    return sums
+
+
+def view_pointwise(img, table, sums=None, part=0, normalize=None):
+    """The operations of one part of every sample's list (0: all, 1: before the blur, 2: after it).  ``normalize`` None:
+    a new uint8 [B,H,W,3]; (mean, std, scale): a new fp32 [B,3,H,W], flipped where the table says so and normalised."""
+    B, H, W = _view_args(img, table)
+    assert sums is None or (sums.dtype == torch.int64 and sums.is_contiguous() and sums.numel() == B)
+    if normalize is None:
+        out = torch.empty(B, H, W, 3, dtype=torch.uint8, device=img.device)
+        consts = None
+    else:
+        mean, std, scale = normalize
+        out = torch.empty(B, 3, H, W, dtype=torch.float32, device=img.device)
+        consts = C.cast((C.c_float * 7)(*[float(v) for v in mean], *[float(v) for v in std], float(scale)), C.c_void_p)
+    view_pointwise_into(img, table, sums, part, out, consts)
+    return out
+
+
+def view_pointwise_into(img, table, sums, part, out, consts):
+    """``out``: a uint8 [B,H,W,3] or fp32 [B,3,H,W] tensor (any 4-byte aligned address: a view is fine); consts: the
+    7 host floats as a c_void_p, for the fp32 output."""
+    B, H, W = _view_args(img, table)
+    if B == 0:
+        return out
+    u8 = out.dtype == torch.uint8
+    L.check(_lib().passl_hip_view_pointwise(L.ptr(img), L.ptr(table), L.ptr(sums), L.ptr(out) if u8 else None,
+                                            None if u8 else L.ptr(out), B, H, W, int(part), consts, L.stream()),
+            'view_pointwise')
+    return out
+
+
+def gaussian_blur_u8(img, table, r_max):
+    """img uint8 [B,H,W,3] -> a new uint8 [B,H,W,3]: samples whose row carries r >= 0 blurred (three box passes per axis
+    with the row's (r, ww, fw)), the others copied.  ``r_max``: the largest r of the table, known to the caller."""
+    B, H, W = _view_args(img, table)
+    if int(r_max) > BLUR_R_MAX:
+        raise L.PasslHipError('gaussian_blur_u8: a box radius of %d is outside the built envelope (<= %d)'
+                              % (int(r_max), BLUR_R_MAX))
+    out = torch.empty_like(img)
+    if B:
+        L.check(_lib().passl_hip_gaussian_blur_u8(L.ptr(img), L.ptr(out), L.ptr(table), B, H, W, int(r_max), L.stream()),
+                'gaussian_blur_u8')
+    return out
+
+
 def soft_ce_fwd(scores, target):
     """scores, target fp32 [N,C] -> out[3] = (loss, acc1 %, acc5 % against argmax target), lse [N], tsum [N]."""
     assert scores.shape == target.shape and target.dtype == torch.float32
