@@ -628,11 +628,6 @@ static inline int grid_for(int64_t n) {
 
 }  // namespace
 
-#define DISPATCH_DTYPE(dtype, ...)                          \
-  if ((dtype) == PASSL_BF16) { using T = bf16_t; __VA_ARGS__ } \
-  else if ((dtype) == PASSL_F32) { using T = float; __VA_ARGS__ } \
-  else return PASSL_EUNSUPPORTED;
-
 // row segments of a slab: one per kFinSegRows* rows (one round trip of loads per block), at most kFinSegMax
 static int fin_segments(int nblocks, bool shifted, int* seg_rows) {
   const int per = shifted ? kFinSegRowsFwd : kFinSegRowsBwd;
@@ -683,10 +678,10 @@ extern "C" int passl_hip_bn_stats(const void* x, float* partial, int64_t M, int 
   if (!x || !partial || M <= 0 || C <= 0 || (C & 7) || nblocks <= 0 || !aligned16(x))
     return PASSL_EINVAL;
   const int rows = (int)((M + nblocks - 1) / nblocks);
-  DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((bn_reduce_kernel<T, 0>), dim3(nblocks), dim3(kThreads),
-                                           kThreads * 16 * sizeof(float), as_stream(stream),
-                                           reinterpret_cast<const T*>(x), nullptr, nullptr, nullptr,
-                                           nullptr, nullptr, nullptr, partial, M, C, rows, 0);)
+  PASSL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((bn_reduce_kernel<T, 0>), dim3(nblocks), dim3(kThreads),
+                                                 kThreads * 16 * sizeof(float), as_stream(stream),
+                                                 reinterpret_cast<const T*>(x), nullptr, nullptr, nullptr,
+                                                 nullptr, nullptr, nullptr, partial, M, C, rows, 0);)
   PASSL_RETURN_IF_LAUNCH_FAILED();
   return PASSL_OK;
 }
@@ -724,22 +719,22 @@ extern "C" int passl_hip_bn_apply(const void* x, const float* scale, const float
   const int64_t nchunks = M * (C >> 3);
   const int U = (kThreads % (C >> 3)) == 0 ? passl_opt(Opt::bn_stream_unroll) : 0;
 #define PASSL_BN_APPLY_TILE(UU)                                                                          \
-  DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((bn_apply_tile_kernel<T, UU>),                               \
-                                           dim3((unsigned)((nchunks + kThreads * UU - 1) / (kThreads * UU))), \
-                                           dim3(kThreads), 0, as_stream(stream),                        \
-                                           reinterpret_cast<const T*>(x), scale, shift,                 \
-                                           reinterpret_cast<const T*>(residual),                        \
-                                           reinterpret_cast<T*>(z), relu_mask, nchunks, C >> 3, relu);)
+  PASSL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((bn_apply_tile_kernel<T, UU>),                         \
+                                                 dim3((unsigned)((nchunks + kThreads * UU - 1) / (kThreads * UU))), \
+                                                 dim3(kThreads), 0, as_stream(stream),                  \
+                                                 reinterpret_cast<const T*>(x), scale, shift,           \
+                                                 reinterpret_cast<const T*>(residual),                  \
+                                                 reinterpret_cast<T*>(z), relu_mask, nchunks, C >> 3, relu);)
   if (U == 2) { PASSL_BN_APPLY_TILE(2) }
   else if (U == 4) { PASSL_BN_APPLY_TILE(4) }
   else if (U == 8) { PASSL_BN_APPLY_TILE(8) }
   else {
-    DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(bn_apply_kernel<T>, dim3(grid_for(nchunks)),
-                                             dim3(kThreads), 0, as_stream(stream),
-                                             reinterpret_cast<const T*>(x), scale, shift,
-                                             reinterpret_cast<const T*>(residual),
-                                             reinterpret_cast<T*>(z), relu_mask, nchunks, C >> 3,
-                                             relu);)
+    PASSL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(bn_apply_kernel<T>, dim3(grid_for(nchunks)),
+                                                   dim3(kThreads), 0, as_stream(stream),
+                                                   reinterpret_cast<const T*>(x), scale, shift,
+                                                   reinterpret_cast<const T*>(residual),
+                                                   reinterpret_cast<T*>(z), relu_mask, nchunks, C >> 3,
+                                                   relu);)
   }
 #undef PASSL_BN_APPLY_TILE
   PASSL_RETURN_IF_LAUNCH_FAILED();
@@ -763,11 +758,11 @@ extern "C" int passl_hip_bn_bwd_reduce(const void* dz, const void* z, const void
       M <= 0 || C <= 0 || (C & 7) || nblocks <= 0 || !aligned16(dz) || !aligned16(x))
     return PASSL_EINVAL;
   const int rows = (int)((M + nblocks - 1) / nblocks);
-  DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((bn_reduce_kernel<T, 1>), dim3(nblocks), dim3(kThreads),
-                                           kThreads * 16 * sizeof(float), as_stream(stream),
-                                           reinterpret_cast<const T*>(x),
-                                           reinterpret_cast<const T*>(dz), z, mean, invstd, scale,
-                                           shift, partial, M, C, rows, relu);)
+  PASSL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((bn_reduce_kernel<T, 1>), dim3(nblocks), dim3(kThreads),
+                                                 kThreads * 16 * sizeof(float), as_stream(stream),
+                                                 reinterpret_cast<const T*>(x),
+                                                 reinterpret_cast<const T*>(dz), z, mean, invstd, scale,
+                                                 shift, partial, M, C, rows, relu);)
   PASSL_RETURN_IF_LAUNCH_FAILED();
   return PASSL_OK;
 }
@@ -857,23 +852,23 @@ extern "C" int passl_hip_bn_bwd_apply(const void* dz, const void* z, const void*
   const int64_t nchunks = M * (C >> 3);
   const int U = (kThreads % (C >> 3)) == 0 ? passl_opt(Opt::bn_stream_unroll) : 0;
 #define PASSL_BN_BWD_APPLY_TILE(UU)                                                                      \
-  DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((bn_bwd_apply_tile_kernel<T, UU>),                           \
-                                           dim3((unsigned)((nchunks + kThreads * UU - 1) / (kThreads * UU))), \
-                                           dim3(kThreads), 0, as_stream(stream),                        \
-                                           reinterpret_cast<const T*>(dz), z,                           \
-                                           reinterpret_cast<const T*>(x), coef, scale, shift,           \
-                                           reinterpret_cast<T*>(dx), reinterpret_cast<T*>(dres),        \
-                                           nchunks, C >> 3, C, relu);)
+  PASSL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((bn_bwd_apply_tile_kernel<T, UU>),                     \
+                                                 dim3((unsigned)((nchunks + kThreads * UU - 1) / (kThreads * UU))), \
+                                                 dim3(kThreads), 0, as_stream(stream),                  \
+                                                 reinterpret_cast<const T*>(dz), z,                     \
+                                                 reinterpret_cast<const T*>(x), coef, scale, shift,     \
+                                                 reinterpret_cast<T*>(dx), reinterpret_cast<T*>(dres),  \
+                                                 nchunks, C >> 3, C, relu);)
   if (U == 2) { PASSL_BN_BWD_APPLY_TILE(2) }
   else if (U == 4) { PASSL_BN_BWD_APPLY_TILE(4) }
   else if (U == 8) { PASSL_BN_BWD_APPLY_TILE(8) }
   else {
-    DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3(grid_for(nchunks)),
-                                             dim3(kThreads), 0, as_stream(stream),
-                                             reinterpret_cast<const T*>(dz), z,
-                                             reinterpret_cast<const T*>(x), coef, scale, shift,
-                                             reinterpret_cast<T*>(dx), reinterpret_cast<T*>(dres),
-                                             nchunks, C >> 3, C, relu);)
+    PASSL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3(grid_for(nchunks)),
+                                                   dim3(kThreads), 0, as_stream(stream),
+                                                   reinterpret_cast<const T*>(dz), z,
+                                                   reinterpret_cast<const T*>(x), coef, scale, shift,
+                                                   reinterpret_cast<T*>(dx), reinterpret_cast<T*>(dres),
+                                                   nchunks, C >> 3, C, relu);)
   }
 #undef PASSL_BN_BWD_APPLY_TILE
   PASSL_RETURN_IF_LAUNCH_FAILED();

@@ -9,6 +9,7 @@
 // A label outside [0, C) makes the loss NaN (the reference raises inside Paddle's kernel).
 #include <math.h>
 #include "common.h"
+#include "terms_finish.h"
 
 namespace {
 
@@ -46,16 +47,6 @@ __global__ void __launch_bounds__(kThreads) softmax_ce_fwd_kernel(const float* _
   }
 }
 
-// out[k] = sum_i terms[k][i] in one fixed order (wave k)
-__global__ void __launch_bounds__(192) softmax_ce_finish_kernel(const float* __restrict__ terms, int N,
-                                                                float* __restrict__ out) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  float a = 0.f;
-  for (int i = lane; i < N; i += 64) a += terms[(int64_t)w * N + i];
-  a = wave_sum(a);
-  if (lane == 0) out[w] = a;
-}
-
 // ds[i][j] = g/N (exp(s_ij - lse_i) - [j == label_i])
 __global__ void __launch_bounds__(kThreads) softmax_ce_bwd_kernel(const float* __restrict__ s,
                                                                   const float* __restrict__ lse,
@@ -82,7 +73,7 @@ extern "C" int passl_hip_softmax_ce_fwd(const float* scores, const int64_t* labe
   hipStream_t st = as_stream(stream);
   hipLaunchKernelGGL(softmax_ce_fwd_kernel, dim3((N + 3) / 4), dim3(kThreads), 0, st, scores, labels, N,
                      C, lse, ws);
-  hipLaunchKernelGGL(softmax_ce_finish_kernel, dim3(1), dim3(192), 0, st, ws, N, out);
+  hipLaunchKernelGGL(terms_finish_kernel<3>, dim3(1), dim3(192), 0, st, ws, N, out);
   PASSL_RETURN_IF_LAUNCH_FAILED();
   return PASSL_OK;
 }

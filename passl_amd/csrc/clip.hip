@@ -19,6 +19,7 @@
 //   d I^ = exp(s) G T^,  d T^ = exp(s) G^T I^,  d s = sum(G .* L),  d x = (d x^ - x^ <x^, d x^>) / ||x||.
 #include <climits>
 #include "common.h"
+#include "eltwise.h"
 
 namespace {
 
@@ -30,48 +31,16 @@ inline unsigned grid_for(int64_t n, int per_block = kThreads) {
   return (unsigned)(g < 1 ? 1 : g);
 }
 
-#define CLIP_DISPATCH(dtype, ...)                              \
-  if ((dtype) == PASSL_BF16) { typedef bf16_t T; __VA_ARGS__ } \
-  else if ((dtype) == PASSL_F32) { typedef float T; __VA_ARGS__ } \
-  else return PASSL_EUNSUPPORTED;
-
 // ------------------------------------------------------------------ QuickGELU
 __device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + __expf(-x)); }
 
-// tile form (see gelu_kernel, vit.hip): U x 256 consecutive chunks per workgroup, loads back to back
-constexpr int kEltU = 4;
-
-template <typename T, bool BWD>
-__global__ void __launch_bounds__(kThreads) quick_gelu_kernel(const T* __restrict__ x,
-                                                              const T* __restrict__ dy,
-                                                              T* __restrict__ out, int64_t nchunks) {
-  const int64_t base = (int64_t)blockIdx.x * (kThreads * kEltU) + threadIdx.x;
-  float v[kEltU][8], d[kEltU][8];
-#pragma unroll
-  for (int u = 0; u < kEltU; ++u) {
-    const int64_t i = base + u * kThreads;
-    const int64_t ic = i < nchunks ? i : nchunks - 1;
-    ElemTraits<T>::load8(x + ic * 8, v[u]);
-    if (BWD) ElemTraits<T>::load8(dy + ic * 8, d[u]);
+struct QuickGeluOp {
+  __device__ static __forceinline__ float fwd(float x) { return x * sigm(1.702f * x); }
+  __device__ static __forceinline__ float grad(float x) {
+    const float sg = sigm(1.702f * x);
+    return sg + 1.702f * x * sg * (1.0f - sg);
   }
-#pragma unroll
-  for (int u = 0; u < kEltU; ++u) {
-    const int64_t i = base + u * kThreads;
-    if (i >= nchunks) break;
-    float o[8];
-    if (BWD) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float sg = sigm(1.702f * v[u][e]);
-        o[e] = d[u][e] * (sg + 1.702f * v[u][e] * sg * (1.0f - sg));
-      }
-    } else {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = v[u][e] * sigm(1.702f * v[u][e]);
-    }
-    ElemTraits<T>::store8(out + i * 8, o);
-  }
-}
+};
 
 // ------------------------------------------------------------------ token embedding
 // out[(b*Tn + t)][c] = E[text[b][t]][c] + pos[t][c]   (fp32 tables, output in the compute dtype)
@@ -479,25 +448,12 @@ __global__ void dot_finish_kernel(const float* __restrict__ partial, int n, floa
 
 extern "C" int passl_hip_quick_gelu_fwd(const void* x, void* y, int64_t n, int dtype,
                                         passl_stream_t stream) {
-  if (!x || !y || n <= 0 || (n & 7) || !aligned16(x) || !aligned16(y)) return PASSL_EINVAL;
-  CLIP_DISPATCH(dtype, hipLaunchKernelGGL((quick_gelu_kernel<T, false>), dim3((unsigned)(((n >> 3) + kThreads * kEltU - 1) / (kThreads * kEltU))),
-                                          dim3(kThreads), 0, as_stream(stream),
-                                          reinterpret_cast<const T*>(x), nullptr,
-                                          reinterpret_cast<T*>(y), n >> 3);)
-  PASSL_RETURN_IF_LAUNCH_FAILED();
-  return PASSL_OK;
+  return launch_unary<QuickGeluOp, false>(x, nullptr, y, n, dtype, stream);
 }
 
 extern "C" int passl_hip_quick_gelu_bwd(const void* dy, const void* x, void* dx, int64_t n, int dtype,
                                         passl_stream_t stream) {
-  if (!dy || !x || !dx || n <= 0 || (n & 7) || !aligned16(x) || !aligned16(dy) || !aligned16(dx))
-    return PASSL_EINVAL;
-  CLIP_DISPATCH(dtype, hipLaunchKernelGGL((quick_gelu_kernel<T, true>), dim3((unsigned)(((n >> 3) + kThreads * kEltU - 1) / (kThreads * kEltU))),
-                                          dim3(kThreads), 0, as_stream(stream),
-                                          reinterpret_cast<const T*>(x), reinterpret_cast<const T*>(dy),
-                                          reinterpret_cast<T*>(dx), n >> 3);)
-  PASSL_RETURN_IF_LAUNCH_FAILED();
-  return PASSL_OK;
+  return launch_unary<QuickGeluOp, true>(x, dy, dx, n, dtype, stream);
 }
 
 extern "C" int passl_hip_embed_fwd(const int64_t* text, const float* table, const float* pos, void* out,
@@ -506,9 +462,9 @@ extern "C" int passl_hip_embed_fwd(const int64_t* text, const float* table, cons
       !aligned16(table) || !aligned16(pos) || !aligned16(out))
     return PASSL_EINVAL;
   const int64_t rows = (int64_t)B * T_;
-  CLIP_DISPATCH(dtype, hipLaunchKernelGGL(embed_fwd_kernel<T>, dim3(grid_for(rows * (C >> 3))),
-                                          dim3(kThreads), 0, as_stream(stream), text, table, pos,
-                                          reinterpret_cast<T*>(out), rows, T_, C, vocab);)
+  PASSL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(embed_fwd_kernel<T>, dim3(grid_for(rows * (C >> 3))),
+                                                 dim3(kThreads), 0, as_stream(stream), text, table, pos,
+                                                 reinterpret_cast<T*>(out), rows, T_, C, vocab);)
   PASSL_RETURN_IF_LAUNCH_FAILED();
   return PASSL_OK;
 }
@@ -553,12 +509,12 @@ extern "C" int passl_hip_embed_bwd(const int64_t* text, const void* dout, float*
   uint32_t* amax = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(touched) + (((int64_t)vocab * 4 + 15) / 16) * 16);
   const int64_t nchunks = (int64_t)B * T_ * chunks;
   if (passl_rec::memset_async(amax, 0, sizeof(uint32_t), st) != hipSuccess) return PASSL_ELAUNCH;
-  CLIP_DISPATCH(dtype,
-                hipLaunchKernelGGL(embed_absmax_kernel<T>, dim3(grid_for(nchunks)), dim3(kThreads), 0, st,
-                                   reinterpret_cast<const T*>(dout), nchunks, amax);
-                hipLaunchKernelGGL(embed_scatter_kernel<T>, dim3(T_, slabs), dim3(kThreads),
-                                   (size_t)rows_par * C * sizeof(float), st, text,
-                                   reinterpret_cast<const T*>(dout), amax, acc64, touched, ws, B, T_, C, vocab);)
+  PASSL_DISPATCH_DTYPE(dtype,
+                       hipLaunchKernelGGL(embed_absmax_kernel<T>, dim3(grid_for(nchunks)), dim3(kThreads), 0, st,
+                                          reinterpret_cast<const T*>(dout), nchunks, amax);
+                       hipLaunchKernelGGL(embed_scatter_kernel<T>, dim3(T_, slabs), dim3(kThreads),
+                                          (size_t)rows_par * C * sizeof(float), st, text,
+                                          reinterpret_cast<const T*>(dout), amax, acc64, touched, ws, B, T_, C, vocab);)
   hipLaunchKernelGGL(embed_flush_kernel, dim3((vocab + 3) / 4), dim3(kThreads), 0, st, acc64, touched, amax,
                      dtable, vocab, C, (int64_t)B * T_);
   PASSL_RETURN_IF_LAUNCH_FAILED();
@@ -569,11 +525,11 @@ extern "C" int passl_hip_gather_rows(const void* x, const int32_t* idx, void* ou
                                      int dtype, passl_stream_t stream) {
   if (!x || !idx || !out || n <= 0 || C <= 0 || (C & 7) || !aligned16(x) || !aligned16(out))
     return PASSL_EINVAL;
-  CLIP_DISPATCH(dtype, hipLaunchKernelGGL(gather_rows_kernel<T>,
-                                          dim3(grid_for((int64_t)n * (C / ElemTraits<T>::VEC))),
-                                          dim3(kThreads), 0, as_stream(stream),
-                                          reinterpret_cast<const T*>(x), idx, reinterpret_cast<T*>(out),
-                                          n, C);)
+  PASSL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(gather_rows_kernel<T>,
+                                                 dim3(grid_for((int64_t)n * (C / ElemTraits<T>::VEC))),
+                                                 dim3(kThreads), 0, as_stream(stream),
+                                                 reinterpret_cast<const T*>(x), idx, reinterpret_cast<T*>(out),
+                                                 n, C);)
   PASSL_RETURN_IF_LAUNCH_FAILED();
   return PASSL_OK;
 }
@@ -587,10 +543,10 @@ extern "C" int passl_hip_scatter_rows(const void* dout, const int32_t* idx, void
   const size_t esz = dtype == PASSL_BF16 ? 2 : 4;
   if (dtype != PASSL_BF16 && dtype != PASSL_F32) return PASSL_EUNSUPPORTED;
   if (passl_rec::memset_async(dx, 0, (size_t)rows_total * C * esz, st) != hipSuccess) return PASSL_ELAUNCH;
-  CLIP_DISPATCH(dtype, hipLaunchKernelGGL(scatter_rows_kernel<T>,
-                                          dim3(grid_for((int64_t)n * (C / ElemTraits<T>::VEC))),
-                                          dim3(kThreads), 0, st, reinterpret_cast<const T*>(dout), idx,
-                                          reinterpret_cast<T*>(dx), n, C);)
+  PASSL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(scatter_rows_kernel<T>,
+                                                 dim3(grid_for((int64_t)n * (C / ElemTraits<T>::VEC))),
+                                                 dim3(kThreads), 0, st, reinterpret_cast<const T*>(dout), idx,
+                                                 reinterpret_cast<T*>(dx), n, C);)
   PASSL_RETURN_IF_LAUNCH_FAILED();
   return PASSL_OK;
 }

@@ -14,6 +14,13 @@ typedef unsigned short bf16_t;   // raw bf16 bits
     if (hipGetLastError() != hipSuccess) return PASSL_ELAUNCH; \
   } while (0)
 
+// Host side of an entry point with a `dtype` argument: runs the statements with T = the element type,
+// or returns PASSL_EUNSUPPORTED from the enclosing function.
+#define PASSL_DISPATCH_DTYPE(dtype, ...)                          \
+  if ((dtype) == PASSL_BF16) { using T = bf16_t; __VA_ARGS__ }    \
+  else if ((dtype) == PASSL_F32) { using T = float; __VA_ARGS__ } \
+  else return PASSL_EUNSUPPORTED;
+
 static inline hipStream_t as_stream(passl_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 __device__ __forceinline__ float bf2f(bf16_t h) { return __uint_as_float(((uint32_t)h) << 16); }

@@ -131,11 +131,6 @@ static int stream_geometry(int B, int T, int C, float keep_prob, int* per, int* 
 
 }  // namespace
 
-#define DROP_PATH_DISPATCH(dtype, ...)                           \
-  if ((dtype) == PASSL_BF16) { using T = bf16_t; __VA_ARGS__ }   \
-  else if ((dtype) == PASSL_F32) { using T = float; __VA_ARGS__ } \
-  else return PASSL_EUNSUPPORTED;
-
 extern "C" int passl_hip_drop_path_draw(float* keep, const float* keep_prob, int slots, int B, int64_t seed,
                                         int64_t* step, passl_stream_t stream) {
   if (!keep || !keep_prob || !step || slots <= 0 || B <= 0 || (reinterpret_cast<uintptr_t>(step) & 7))
@@ -154,10 +149,10 @@ extern "C" int passl_hip_drop_path_add(const void* branch, const void* residual,
   int per = 0, tiles = 0;
   const int rc = stream_geometry(B, T, C, keep_prob, &per, &tiles);
   if (rc != PASSL_OK) return rc;
-  DROP_PATH_DISPATCH(dtype, hipLaunchKernelGGL(drop_path_add_kernel<T>, dim3((unsigned)(tiles * B)), dim3(kThreads), 0,
-                                               as_stream(stream), reinterpret_cast<const T*>(branch),
-                                               reinterpret_cast<const T*>(residual), keep, keep_prob,
-                                               reinterpret_cast<T*>(out), per, tiles);)
+  PASSL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(drop_path_add_kernel<T>, dim3((unsigned)(tiles * B)), dim3(kThreads), 0,
+                                                 as_stream(stream), reinterpret_cast<const T*>(branch),
+                                                 reinterpret_cast<const T*>(residual), keep, keep_prob,
+                                                 reinterpret_cast<T*>(out), per, tiles);)
   PASSL_RETURN_IF_LAUNCH_FAILED();
   return PASSL_OK;
 }
@@ -168,9 +163,9 @@ extern "C" int passl_hip_drop_path_bwd(const void* dy, const float* keep, float 
   int per = 0, tiles = 0;
   const int rc = stream_geometry(B, T, C, keep_prob, &per, &tiles);
   if (rc != PASSL_OK) return rc;
-  DROP_PATH_DISPATCH(dtype, hipLaunchKernelGGL(drop_path_bwd_kernel<T>, dim3((unsigned)(tiles * B)), dim3(kThreads), 0,
-                                               as_stream(stream), reinterpret_cast<const T*>(dy), keep, keep_prob,
-                                               reinterpret_cast<T*>(dbranch), per, tiles);)
+  PASSL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(drop_path_bwd_kernel<T>, dim3((unsigned)(tiles * B)), dim3(kThreads), 0,
+                                                 as_stream(stream), reinterpret_cast<const T*>(dy), keep, keep_prob,
+                                                 reinterpret_cast<T*>(dbranch), per, tiles);)
   PASSL_RETURN_IF_LAUNCH_FAILED();
   return PASSL_OK;
 }

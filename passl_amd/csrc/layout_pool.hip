@@ -273,11 +273,6 @@ static inline int grid_for(int64_t n) {
 
 }  // namespace
 
-#define DISPATCH_DTYPE(dtype, ...)                          \
-  if ((dtype) == PASSL_BF16) { using T = bf16_t; __VA_ARGS__ } \
-  else if ((dtype) == PASSL_F32) { using T = float; __VA_ARGS__ } \
-  else return PASSL_EUNSUPPORTED;
-
 extern "C" int passl_hip_nchw_to_nhwc_pad(const float* x, void* y, int N, int C, int H, int W,
                                           int pad, int Wp, int Cp, int dtype,
                                           passl_stream_t stream) {
@@ -292,9 +287,9 @@ extern "C" int passl_hip_nchw_to_nhwc_pad(const float* x, void* y, int N, int C,
     PASSL_RETURN_IF_LAUNCH_FAILED();
     return PASSL_OK;
   }
-  DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(nchw_to_nhwc_pad_kernel<T>, dim3(grid_for(total)),
-                                           dim3(kThreads), 0, as_stream(stream), x,
-                                           reinterpret_cast<T*>(y), N, C, H, W, pad, Hp, Wp, Cp);)
+  PASSL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(nchw_to_nhwc_pad_kernel<T>, dim3(grid_for(total)),
+                                                 dim3(kThreads), 0, as_stream(stream), x,
+                                                 reinterpret_cast<T*>(y), N, C, H, W, pad, Hp, Wp, Cp);)
   PASSL_RETURN_IF_LAUNCH_FAILED();
   return PASSL_OK;
 }
@@ -307,10 +302,10 @@ extern "C" int passl_hip_maxpool3x3s2_fwd(const void* x, void* y, uint8_t* idx, 
   const int P = (H + 2 - 3) / 2 + 1, Q = (W + 2 - 3) / 2 + 1;
   const int64_t total = (int64_t)N * P * Q * (C >> 3);
   if (total > 0x7fffffffll) return PASSL_EUNSUPPORTED;       // the kernels index with 32 bits
-  DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(maxpool_fwd_kernel<T>, dim3((unsigned)((total + kThreads - 1) / kThreads)),
-                                           dim3(kThreads), 0, as_stream(stream),
-                                           reinterpret_cast<const T*>(x), reinterpret_cast<T*>(y),
-                                           idx, N, H, W, C, P, Q);)
+  PASSL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(maxpool_fwd_kernel<T>, dim3((unsigned)((total + kThreads - 1) / kThreads)),
+                                                 dim3(kThreads), 0, as_stream(stream),
+                                                 reinterpret_cast<const T*>(x), reinterpret_cast<T*>(y),
+                                                 idx, N, H, W, C, P, Q);)
   PASSL_RETURN_IF_LAUNCH_FAILED();
   return PASSL_OK;
 }
@@ -323,10 +318,10 @@ extern "C" int passl_hip_maxpool3x3s2_bwd(const void* dy, const uint8_t* idx, vo
   const int P = (H + 2 - 3) / 2 + 1, Q = (W + 2 - 3) / 2 + 1;
   const int64_t total = (int64_t)N * ((H + 1) / 2) * ((W + 1) / 2) * (C >> 3);   // 2 x 2 input pixels per thread
   if (total > 0x7fffffffll) return PASSL_EUNSUPPORTED;       // the kernels index with 32 bits
-  DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(maxpool_bwd_kernel<T>, dim3((unsigned)((total + kThreads - 1) / kThreads)),
-                                           dim3(kThreads), 0, as_stream(stream),
-                                           reinterpret_cast<const T*>(dy), idx,
-                                           reinterpret_cast<T*>(dx), N, H, W, C, P, Q);)
+  PASSL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(maxpool_bwd_kernel<T>, dim3((unsigned)((total + kThreads - 1) / kThreads)),
+                                                 dim3(kThreads), 0, as_stream(stream),
+                                                 reinterpret_cast<const T*>(dy), idx,
+                                                 reinterpret_cast<T*>(dx), N, H, W, C, P, Q);)
   PASSL_RETURN_IF_LAUNCH_FAILED();
   return PASSL_OK;
 }
@@ -337,9 +332,9 @@ extern "C" int passl_hip_avgpool_fwd(const void* x, void* y, int N, int HW, int 
     return PASSL_EINVAL;
   const int64_t total = (int64_t)N * (C >> 3);
   const int grid = (int)((total + kThreads - 1) / kThreads);
-  DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(avgpool_fwd_kernel<T>, dim3(grid), dim3(kThreads), 0,
-                                           as_stream(stream), reinterpret_cast<const T*>(x),
-                                           reinterpret_cast<T*>(y), N, HW, C);)
+  PASSL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(avgpool_fwd_kernel<T>, dim3(grid), dim3(kThreads), 0,
+                                                 as_stream(stream), reinterpret_cast<const T*>(x),
+                                                 reinterpret_cast<T*>(y), N, HW, C);)
   PASSL_RETURN_IF_LAUNCH_FAILED();
   return PASSL_OK;
 }
@@ -349,10 +344,10 @@ extern "C" int passl_hip_avgpool_bwd(const void* dy, void* dx, int N, int HW, in
   if (!dy || !dx || N <= 0 || HW <= 0 || C <= 0 || (C & 7) || !aligned16(dy) || !aligned16(dx))
     return PASSL_EINVAL;
   const int64_t total = (int64_t)N * HW * (C >> 3);
-  DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(avgpool_bwd_kernel<T>, dim3(grid_for(total)),
-                                           dim3(kThreads), 0, as_stream(stream),
-                                           reinterpret_cast<const T*>(dy),
-                                           reinterpret_cast<T*>(dx), N, HW, C);)
+  PASSL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(avgpool_bwd_kernel<T>, dim3(grid_for(total)),
+                                                 dim3(kThreads), 0, as_stream(stream),
+                                                 reinterpret_cast<const T*>(dy),
+                                                 reinterpret_cast<T*>(dx), N, HW, C);)
   PASSL_RETURN_IF_LAUNCH_FAILED();
   return PASSL_OK;
 }
@@ -378,9 +373,9 @@ static int colsum_impl(const void* x, float* out, int64_t M, int C, int dtype, b
   } else {
     return PASSL_EINVAL;                                // several row slabs need the workspace (no fp32 atomics)
   }
-  DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(colsum_kernel<T>, dim3((C + 255) / 256, slabs),
-                                           dim3(kThreads), 0, as_stream(stream),
-                                           reinterpret_cast<const T*>(x), out, M, C, rows, mode, ws);)
+  PASSL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(colsum_kernel<T>, dim3((C + 255) / 256, slabs),
+                                                 dim3(kThreads), 0, as_stream(stream),
+                                                 reinterpret_cast<const T*>(x), out, M, C, rows, mode, ws);)
   PASSL_RETURN_IF_LAUNCH_FAILED();
   if (mode == 2) return passl_slab_reduce_launch(ws, out, C, slabs, accumulate ? 1 : 0, as_stream(stream));
   return PASSL_OK;
@@ -401,11 +396,11 @@ extern "C" int passl_hip_relu_bwd(const void* dy, const void* y, void* dx, int64
   if (!dy || !y || !dx || n <= 0 || (n & 7) || !aligned16(dy) || !aligned16(y) || !aligned16(dx))
     return PASSL_EINVAL;
   const int64_t nchunks = n >> 3;
-  DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(relu_bwd_kernel<T>, dim3(grid_for(nchunks)),
-                                           dim3(kThreads), 0, as_stream(stream),
-                                           reinterpret_cast<const T*>(dy),
-                                           reinterpret_cast<const T*>(y),
-                                           reinterpret_cast<T*>(dx), nchunks);)
+  PASSL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(relu_bwd_kernel<T>, dim3(grid_for(nchunks)),
+                                                 dim3(kThreads), 0, as_stream(stream),
+                                                 reinterpret_cast<const T*>(dy),
+                                                 reinterpret_cast<const T*>(y),
+                                                 reinterpret_cast<T*>(dx), nchunks);)
   PASSL_RETURN_IF_LAUNCH_FAILED();
   return PASSL_OK;
 }

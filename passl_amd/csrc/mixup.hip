@@ -17,6 +17,7 @@
 // The cross-entropy keeps the form of clas.hip: one wave per row, per-row terms summed in one fixed order, no atomics.
 #include <math.h>
 #include "common.h"
+#include "terms_finish.h"
 
 namespace {
 
@@ -211,16 +212,6 @@ __global__ void __launch_bounds__(kThreads) soft_ce_fwd_kernel(const float* __re
   }
 }
 
-// out[k] = sum_i terms[k][i] in one fixed order (wave k)
-__global__ void __launch_bounds__(192) soft_ce_finish_kernel(const float* __restrict__ terms, int N,
-                                                             float* __restrict__ out) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  float a = 0.f;
-  for (int i = lane; i < N; i += 64) a += terms[(int64_t)w * N + i];
-  a = wave_sum(a);
-  if (lane == 0) out[w] = a;
-}
-
 // ds[i][j] = g/N (exp(s_ij - lse_i) T_i - t_ij); a chunk lies inside one row (C % VEC == 0)
 template <int VEC>
 __global__ void __launch_bounds__(kThreads) soft_ce_bwd_kernel(const float* __restrict__ s,
@@ -302,7 +293,7 @@ extern "C" int passl_hip_soft_ce_fwd(const float* scores, const float* target, i
   else
     hipLaunchKernelGGL(soft_ce_fwd_kernel<1>, dim3((N + 3) / 4), dim3(kThreads), 0, st, scores, target, N, C, lse, tsum,
                        ws);
-  hipLaunchKernelGGL(soft_ce_finish_kernel, dim3(1), dim3(192), 0, st, ws, N, out);
+  hipLaunchKernelGGL(terms_finish_kernel<3>, dim3(1), dim3(192), 0, st, ws, N, out);
   PASSL_RETURN_IF_LAUNCH_FAILED();
   return PASSL_OK;
 }

@@ -531,11 +531,6 @@ inline bool second_form(int N, int H, int W, int C) {
 
 }  // namespace
 
-#define DISPATCH_DTYPE(dtype, ...)                          \
-  if ((dtype) == PASSL_BF16) { using T = bf16_t; __VA_ARGS__ } \
-  else if ((dtype) == PASSL_F32) { using T = float; __VA_ARGS__ } \
-  else return PASSL_EUNSUPPORTED;
-
 extern "C" int passl_hip_bn_relu_maxpool_blocks(int N, int H, int W, int C) {
   int64_t oi, ii;
   if (!shape_ok(N, H, W, C, &oi, &ii)) return 0;
@@ -552,9 +547,9 @@ extern "C" int passl_hip_bn_relu_maxpool_fwd(const void* x, const float* scale, 
     return PASSL_EINVAL;
   if (!shape_ok(N, H, W, C, &oi, &ii)) return PASSL_EUNSUPPORTED;
   const int P = (H + 2 - 3) / 2 + 1, Q = (W + 2 - 3) / 2 + 1;
-  DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(bn_relu_maxpool_fwd_kernel<T>, dim3((unsigned)((oi + kThreads - 1) / kThreads)),
-                                           dim3(kThreads), 0, as_stream(stream), reinterpret_cast<const T*>(x), scale,
-                                           shift, reinterpret_cast<T*>(y), idx, N, H, W, C, P, Q);)
+  PASSL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(bn_relu_maxpool_fwd_kernel<T>, dim3((unsigned)((oi + kThreads - 1) / kThreads)),
+                                                 dim3(kThreads), 0, as_stream(stream), reinterpret_cast<const T*>(x), scale,
+                                                 shift, reinterpret_cast<T*>(y), idx, N, H, W, C, P, Q);)
   PASSL_RETURN_IF_LAUNCH_FAILED();
   return PASSL_OK;
 }
@@ -573,17 +568,17 @@ extern "C" int passl_hip_bn_relu_maxpool_bwd_reduce(const void* dy, const uint8_
   if (second_form(N, H, W, C)) {
     const v2::Geo g = make_geo(N, H, W, C, ii);
     const unsigned lds = (unsigned)(C * 16 > 16384 ? C * 16 : 16384);
-    DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(v2::bwd_reduce_kernel<T>, dim3((unsigned)nblocks), dim3(kThreads), lds,
-                                             as_stream(stream), reinterpret_cast<const T*>(dy), idx,
-                                             reinterpret_cast<const T*>(x), mean, invstd, scale, shift, partial, g);)
+    PASSL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(v2::bwd_reduce_kernel<T>, dim3((unsigned)nblocks), dim3(kThreads), lds,
+                                                   as_stream(stream), reinterpret_cast<const T*>(dy), idx,
+                                                   reinterpret_cast<const T*>(x), mean, invstd, scale, shift, partial, g);)
     PASSL_RETURN_IF_LAUNCH_FAILED();
     return PASSL_OK;
   }
   const int P = (H + 2 - 3) / 2 + 1, Q = (W + 2 - 3) / 2 + 1;
-  DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(bn_relu_maxpool_bwd_reduce_kernel<T>, dim3((unsigned)nblocks), dim3(kThreads), 0,
-                                           as_stream(stream), reinterpret_cast<const T*>(dy), idx,
-                                           reinterpret_cast<const T*>(x), mean, invstd, scale, shift, partial, N, H, W, C,
-                                           P, Q);)
+  PASSL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(bn_relu_maxpool_bwd_reduce_kernel<T>, dim3((unsigned)nblocks), dim3(kThreads), 0,
+                                                 as_stream(stream), reinterpret_cast<const T*>(dy), idx,
+                                                 reinterpret_cast<const T*>(x), mean, invstd, scale, shift, partial, N, H, W, C,
+                                                 P, Q);)
   PASSL_RETURN_IF_LAUNCH_FAILED();
   return PASSL_OK;
 }
@@ -597,10 +592,10 @@ extern "C" int passl_hip_bn_relu_maxpool_bwd_apply(const void* dy, const uint8_t
     return PASSL_EINVAL;
   if (!shape_ok(N, H, W, C, &oi, &ii)) return PASSL_EUNSUPPORTED;
   const int P = (H + 2 - 3) / 2 + 1, Q = (W + 2 - 3) / 2 + 1;
-  DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(bn_relu_maxpool_bwd_apply_kernel<T>, dim3((unsigned)((ii + kThreads - 1) / kThreads)),
-                                           dim3(kThreads), 0, as_stream(stream), reinterpret_cast<const T*>(dy), idx,
-                                           reinterpret_cast<const T*>(x), coef, scale, shift, reinterpret_cast<T*>(dx), N,
-                                           H, W, C, P, Q);)
+  PASSL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(bn_relu_maxpool_bwd_apply_kernel<T>, dim3((unsigned)((ii + kThreads - 1) / kThreads)),
+                                                 dim3(kThreads), 0, as_stream(stream), reinterpret_cast<const T*>(dy), idx,
+                                                 reinterpret_cast<const T*>(x), coef, scale, shift, reinterpret_cast<T*>(dx), N,
+                                                 H, W, C, P, Q);)
   PASSL_RETURN_IF_LAUNCH_FAILED();
   return PASSL_OK;
 }

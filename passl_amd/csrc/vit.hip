@@ -7,14 +7,11 @@
 //   LayerNorm/GELU  :61-85,158-189      random_masking :461-488     forward_encoder :490-510
 //   forward_decoder :512-539            patchify/forward_loss :433-445,541-557
 #include "common.h"
+#include "eltwise.h"
 
 namespace {
 
 constexpr int kThreads = 256;
-
-template <typename T> __device__ __forceinline__ void ld8(const T* p, float (&v)[8]) {
-  ElemTraits<T>::load8(p, v);
-}
 
 // ------------------------------------------------------------------ LayerNorm (one wave per row)
 template <typename T>
@@ -28,7 +25,7 @@ __global__ void __launch_bounds__(kThreads) layernorm_fwd_kernel(
   float s = 0.f, ss = 0.f;
   for (int c = lane * 8; c < C; c += 512) {
     float v[8];
-    ld8(xr + c, v);
+    ElemTraits<T>::load8(xr + c, v);
 #pragma unroll
     for (int e = 0; e < 8; ++e) { s += v[e]; ss += v[e] * v[e]; }
   }
@@ -42,7 +39,7 @@ __global__ void __launch_bounds__(kThreads) layernorm_fwd_kernel(
   T* yr = y + (int64_t)row * C;
   for (int c = lane * 8; c < C; c += 512) {
     float v[8], g[8], b[8];
-    ld8(xr + c, v);
+    ElemTraits<T>::load8(xr + c, v);
     ElemTraits<float>::load8(gamma + c, g);
     ElemTraits<float>::load8(beta + c, b);
 #pragma unroll
@@ -100,11 +97,12 @@ __global__ void __launch_bounds__(kThreads) layernorm_bwd_kernel(
         // out-of-range lanes read a valid address (row r0 / column 0) and are zeroed by a select
         const bool live = ok[u] && c < C;
         const int64_t off = (int64_t)(ok[u] ? rows[u] : r0) * C + (c < C ? c : 0);
-        ld8(x + off, xv[u][k]);
-        ld8(dy + off, dv[u][k]);
+        ElemTraits<T>::load8(x + off, xv[u][k]);
+        ElemTraits<T>::load8(dy + off, dv[u][k]);
         // fetched with the other operands: a load issued after the row reductions would put a
         // second full memory round trip on the critical path of every iteration
-        ld8((dres ? dres : dy) + off, rv[u][k]);          // no residual: a second (L1-resident) read of dy, unused
+        // no residual: a second (L1-resident) read of dy, unused
+        ElemTraits<T>::load8((dres ? dres : dy) + off, rv[u][k]);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           xv[u][k][e] = live ? xv[u][k][e] : 0.f;
@@ -203,67 +201,21 @@ __device__ __forceinline__ float gelu_grad_f(float x) {
   return cdf + x * 0.39894228040143268f * __expf(-0.5f * x * x);
 }
 
-// Tile form (as the BatchNorm streaming kernels, bn.hip): a workgroup owns U x 256 consecutive 16-byte
-// chunks, a lane the chunks base + u * 256; all loads are issued back to back, branch-free (a lane past
-// the end re-reads the last chunk), no loop.
-constexpr int kEltU = 4;
-
-template <typename T, bool BWD>
-__global__ void __launch_bounds__(kThreads) gelu_kernel(const T* __restrict__ x,
-                                                        const T* __restrict__ dy,
-                                                        T* __restrict__ out, int64_t nchunks) {
-  const int64_t base = (int64_t)blockIdx.x * (kThreads * kEltU) + threadIdx.x;
-  float v[kEltU][8], d[kEltU][8];
-#pragma unroll
-  for (int u = 0; u < kEltU; ++u) {
-    const int64_t i = base + u * kThreads;
-    const int64_t ic = i < nchunks ? i : nchunks - 1;
-    ld8(x + ic * 8, v[u]);
-    if (BWD) ld8(dy + ic * 8, d[u]);
-  }
-#pragma unroll
-  for (int u = 0; u < kEltU; ++u) {
-    const int64_t i = base + u * kThreads;
-    if (i >= nchunks) break;
-    float o[8];
-    if (BWD) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = d[u][e] * gelu_grad_f(v[u][e]);
-    } else {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = gelu_f(v[u][e]);
-    }
-    ElemTraits<T>::store8(out + i * 8, o);
-  }
-}
+// operators of the streaming unary kernel (eltwise.h)
+struct GeluOp {
+  __device__ static __forceinline__ float fwd(float x) { return gelu_f(x); }
+  __device__ static __forceinline__ float grad(float x) { return gelu_grad_f(x); }
+};
 
 // tanh / its gradient (the `representation_size` head of the v2 VisionTransformer: tanh(head0(x)),
-// passl/models/vision_transformer.py:340-343); same streaming form as gelu_kernel
-template <typename T, bool BWD>
-__global__ void __launch_bounds__(kThreads) tanh_kernel(const T* __restrict__ x, const T* __restrict__ dy,
-                                                        T* __restrict__ out, int64_t nchunks) {
-  const int64_t base = (int64_t)blockIdx.x * (kThreads * kEltU) + threadIdx.x;
-  float v[kEltU][8], d[kEltU][8];
-#pragma unroll
-  for (int u = 0; u < kEltU; ++u) {
-    const int64_t i = base + u * kThreads;
-    const int64_t ic = i < nchunks ? i : nchunks - 1;
-    ld8(x + ic * 8, v[u]);
-    if (BWD) ld8(dy + ic * 8, d[u]);
+// passl/models/vision_transformer.py:340-343)
+struct TanhOp {
+  __device__ static __forceinline__ float fwd(float x) { return tanhf(x); }
+  __device__ static __forceinline__ float grad(float x) {
+    const float t = tanhf(x);
+    return 1.0f - t * t;
   }
-#pragma unroll
-  for (int u = 0; u < kEltU; ++u) {
-    const int64_t i = base + u * kThreads;
-    if (i >= nchunks) break;
-    float o[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float t = tanhf(v[u][e]);
-      o[e] = BWD ? d[u][e] * (1.0f - t * t) : t;
-    }
-    ElemTraits<T>::store8(out + i * 8, o);
-  }
-}
+};
 
 // ------------------------------------------------------------------ MAE masking
 // rank[i] = #{j : noise[j] < noise[i] or (== and j < i)}  (= ids_restore of argsort(argsort));
@@ -304,7 +256,7 @@ __global__ void __launch_bounds__(kThreads) mae_gather_kernel(
       ElemTraits<float>::load8(cls + c, v);
     } else {
       src = ids_keep[(int64_t)b * K + t - 1];
-      ld8(x + ((int64_t)b * L + src) * D + c, v);
+      ElemTraits<T>::load8(x + ((int64_t)b * L + src) * D + c, v);
       src += 1;
     }
     ElemTraits<float>::load8(pos + (int64_t)src * D + c, p);
@@ -328,7 +280,7 @@ __global__ void __launch_bounds__(kThreads) mae_gather_bwd_kernel(
     const int l = (int)(tok % L), b = (int)(tok / L);
     float v[8];
     const int rank = ids_restore[(int64_t)b * L + l];
-    if (rank < K) ld8(dout + ((int64_t)b * (K + 1) + 1 + rank) * D + c, v);
+    if (rank < K) ElemTraits<T>::load8(dout + ((int64_t)b * (K + 1) + 1 + rank) * D + c, v);
     else {
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = 0.f;
@@ -371,7 +323,7 @@ __global__ void __launch_bounds__(kThreads) mae_unshuffle_kernel(
     float v[8], p[8];
     int r = 0;
     if (t > 0) r = ids_restore[(int64_t)b * L + t - 1] + 1;
-    if (r <= K) ld8(x + ((int64_t)b * (K + 1) + r) * D + c, v);
+    if (r <= K) ElemTraits<T>::load8(x + ((int64_t)b * (K + 1) + r) * D + c, v);
     else ElemTraits<float>::load8(mask_token + c, v);
     ElemTraits<float>::load8(pos + (int64_t)t * D + c, p);
 #pragma unroll
@@ -405,11 +357,11 @@ __global__ void __launch_bounds__(kThreads) mae_unshuffle_bwd_kernel(
       float v[8];
       if (t <= K) {       // destination row t of dx: source position in dout
         const int src = t == 0 ? 0 : 1 + ids_keep[(int64_t)b * K + t - 1];
-        ld8(dout + ((int64_t)b * (L + 1) + src) * D + c, v);
+        ElemTraits<T>::load8(dout + ((int64_t)b * (L + 1) + src) * D + c, v);
         ElemTraits<T>::store8(dx + ((int64_t)b * (K + 1) + t) * D + c, v);
       }
       if (t > 0 && ids_restore[(int64_t)b * L + t - 1] >= K) {
-        ld8(dout + tok * D + c, v);
+        ElemTraits<T>::load8(dout + tok * D + c, v);
 #pragma unroll
         for (int e = 0; e < 8; ++e) acc[e] += v[e];
       }
@@ -626,16 +578,8 @@ static inline int grid_for(int64_t n) {
   if (b < 1) b = 1;
   return (int)b;
 }
-static inline unsigned elt_grid(int64_t nchunks) {
-  return (unsigned)((nchunks + kThreads * kEltU - 1) / (kThreads * kEltU));
-}
 
 }  // namespace
-
-#define VIT_DISPATCH(dtype, ...)                                \
-  if ((dtype) == PASSL_BF16) { using T = bf16_t; __VA_ARGS__ }  \
-  else if ((dtype) == PASSL_F32) { using T = float; __VA_ARGS__ } \
-  else return PASSL_EUNSUPPORTED;
 
 extern "C" int passl_hip_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y,
                                        float* mean, float* rstd, int64_t M, int C, float eps,
@@ -643,10 +587,10 @@ extern "C" int passl_hip_layernorm_fwd(const void* x, const float* gamma, const 
   if (!x || !gamma || !beta || !y || !mean || !rstd || M <= 0 || C <= 0 || (C & 7) ||
       !aligned16(x) || !aligned16(y) || !aligned16(gamma) || !aligned16(beta))
     return PASSL_EINVAL;
-  VIT_DISPATCH(dtype, hipLaunchKernelGGL(layernorm_fwd_kernel<T>, dim3((unsigned)((M + 3) / 4)),
-                                         dim3(kThreads), 0, as_stream(stream),
-                                         reinterpret_cast<const T*>(x), gamma, beta,
-                                         reinterpret_cast<T*>(y), mean, rstd, (int)M, C, eps);)
+  PASSL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(layernorm_fwd_kernel<T>, dim3((unsigned)((M + 3) / 4)),
+                                                 dim3(kThreads), 0, as_stream(stream),
+                                                 reinterpret_cast<const T*>(x), gamma, beta,
+                                                 reinterpret_cast<T*>(y), mean, rstd, (int)M, C, eps);)
   PASSL_RETURN_IF_LAUNCH_FAILED();
   return PASSL_OK;
 }
@@ -679,11 +623,11 @@ extern "C" int passl_hip_layernorm_bwd(const void* dy, const void* x, const floa
   int rows, nb;
   ln_bwd_blocks(M, rows, nb);
 #define LN_BWD_LAUNCH(NCH)                                                                          \
-  VIT_DISPATCH(dtype, hipLaunchKernelGGL((layernorm_bwd_kernel<T, NCH>), dim3(nb), dim3(kThreads),  \
-                                         8 * C * sizeof(float), as_stream(stream),                  \
-                                         reinterpret_cast<const T*>(dy), reinterpret_cast<const T*>(x), \
-                                         gamma, mean, rstd, reinterpret_cast<const T*>(dres),       \
-                                         reinterpret_cast<T*>(dx), ws, (int)M, C, rows);)
+  PASSL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((layernorm_bwd_kernel<T, NCH>), dim3(nb), dim3(kThreads), \
+                                                 8 * C * sizeof(float), as_stream(stream),          \
+                                                 reinterpret_cast<const T*>(dy), reinterpret_cast<const T*>(x), \
+                                                 gamma, mean, rstd, reinterpret_cast<const T*>(dres), \
+                                                 reinterpret_cast<T*>(dx), ws, (int)M, C, rows);)
   if (C <= 512) { LN_BWD_LAUNCH(1) }
   else if (C <= 1024) { LN_BWD_LAUNCH(2) }
   else { LN_BWD_LAUNCH(4) }
@@ -707,45 +651,21 @@ extern "C" int passl_hip_layernorm_param_reduce(const float* ws, int64_t M, int 
 }
 
 extern "C" int passl_hip_gelu_fwd(const void* x, void* y, int64_t n, int dtype, passl_stream_t stream) {
-  if (!x || !y || n <= 0 || (n & 7) || !aligned16(x) || !aligned16(y)) return PASSL_EINVAL;
-  VIT_DISPATCH(dtype, hipLaunchKernelGGL((gelu_kernel<T, false>), dim3(elt_grid(n >> 3)), dim3(kThreads),
-                                         0, as_stream(stream), reinterpret_cast<const T*>(x), nullptr,
-                                         reinterpret_cast<T*>(y), n >> 3);)
-  PASSL_RETURN_IF_LAUNCH_FAILED();
-  return PASSL_OK;
+  return launch_unary<GeluOp, false>(x, nullptr, y, n, dtype, stream);
 }
 
 extern "C" int passl_hip_gelu_bwd(const void* dy, const void* x, void* dx, int64_t n, int dtype,
                                   passl_stream_t stream) {
-  if (!dy || !x || !dx || n <= 0 || (n & 7) || !aligned16(x) || !aligned16(dy) || !aligned16(dx))
-    return PASSL_EINVAL;
-  VIT_DISPATCH(dtype, hipLaunchKernelGGL((gelu_kernel<T, true>), dim3(elt_grid(n >> 3)), dim3(kThreads),
-                                         0, as_stream(stream), reinterpret_cast<const T*>(x),
-                                         reinterpret_cast<const T*>(dy), reinterpret_cast<T*>(dx),
-                                         n >> 3);)
-  PASSL_RETURN_IF_LAUNCH_FAILED();
-  return PASSL_OK;
+  return launch_unary<GeluOp, true>(x, dy, dx, n, dtype, stream);
 }
 
 extern "C" int passl_hip_tanh_fwd(const void* x, void* y, int64_t n, int dtype, passl_stream_t stream) {
-  if (!x || !y || n <= 0 || (n & 7) || !aligned16(x) || !aligned16(y)) return PASSL_EINVAL;
-  VIT_DISPATCH(dtype, hipLaunchKernelGGL((tanh_kernel<T, false>), dim3(elt_grid(n >> 3)), dim3(kThreads),
-                                         0, as_stream(stream), reinterpret_cast<const T*>(x), nullptr,
-                                         reinterpret_cast<T*>(y), n >> 3);)
-  PASSL_RETURN_IF_LAUNCH_FAILED();
-  return PASSL_OK;
+  return launch_unary<TanhOp, false>(x, nullptr, y, n, dtype, stream);
 }
 
 extern "C" int passl_hip_tanh_bwd(const void* dy, const void* x, void* dx, int64_t n, int dtype,
                                   passl_stream_t stream) {
-  if (!dy || !x || !dx || n <= 0 || (n & 7) || !aligned16(x) || !aligned16(dy) || !aligned16(dx))
-    return PASSL_EINVAL;
-  VIT_DISPATCH(dtype, hipLaunchKernelGGL((tanh_kernel<T, true>), dim3(elt_grid(n >> 3)), dim3(kThreads),
-                                         0, as_stream(stream), reinterpret_cast<const T*>(x),
-                                         reinterpret_cast<const T*>(dy), reinterpret_cast<T*>(dx),
-                                         n >> 3);)
-  PASSL_RETURN_IF_LAUNCH_FAILED();
-  return PASSL_OK;
+  return launch_unary<TanhOp, true>(x, dy, dx, n, dtype, stream);
 }
 
 extern "C" int passl_hip_mae_mask(const float* noise, int B, int L, int len_keep, int32_t* ids_keep,
@@ -764,10 +684,10 @@ extern "C" int passl_hip_mae_gather(const void* x, const float* cls, const float
                                     int dtype, passl_stream_t stream) {
   if (!x || !cls || !pos || !ids_keep || !out || B <= 0 || L <= 0 || K <= 0 || K > L || D <= 0 || (D & 7))
     return PASSL_EINVAL;
-  VIT_DISPATCH(dtype, hipLaunchKernelGGL(mae_gather_kernel<T>, dim3(grid_for((int64_t)B * (K + 1) * (D >> 3))),
-                                         dim3(kThreads), 0, as_stream(stream),
-                                         reinterpret_cast<const T*>(x), cls, pos, ids_keep,
-                                         reinterpret_cast<T*>(out), B, L, K, D);)
+  PASSL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(mae_gather_kernel<T>, dim3(grid_for((int64_t)B * (K + 1) * (D >> 3))),
+                                                 dim3(kThreads), 0, as_stream(stream),
+                                                 reinterpret_cast<const T*>(x), cls, pos, ids_keep,
+                                                 reinterpret_cast<T*>(out), B, L, K, D);)
   PASSL_RETURN_IF_LAUNCH_FAILED();
   return PASSL_OK;
 }
@@ -777,12 +697,12 @@ extern "C" int passl_hip_mae_gather_bwd(const void* dout, const int32_t* ids_res
                                         passl_stream_t stream) {
   if (!dout || !ids_restore || !dx || !dcls || B <= 0 || L <= 0 || K <= 0 || K > L || D <= 0 || (D & 7))
     return PASSL_EINVAL;
-  VIT_DISPATCH(dtype, hipLaunchKernelGGL(mae_gather_bwd_kernel<T>,
-                                         dim3(grid_for((int64_t)B * L * (D >> 3))), dim3(kThreads), 0,
-                                         as_stream(stream), reinterpret_cast<const T*>(dout), ids_restore,
-                                         reinterpret_cast<T*>(dx), B, L, K, D);
-               hipLaunchKernelGGL(cls_grad_kernel<T>, dim3((D + 31) / 32), dim3(kThreads), 0, as_stream(stream),
-                                  reinterpret_cast<const T*>(dout), dcls, B, (int64_t)(K + 1) * D, D);)
+  PASSL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(mae_gather_bwd_kernel<T>,
+                                                 dim3(grid_for((int64_t)B * L * (D >> 3))), dim3(kThreads), 0,
+                                                 as_stream(stream), reinterpret_cast<const T*>(dout), ids_restore,
+                                                 reinterpret_cast<T*>(dx), B, L, K, D);
+                       hipLaunchKernelGGL(cls_grad_kernel<T>, dim3((D + 31) / 32), dim3(kThreads), 0, as_stream(stream),
+                                          reinterpret_cast<const T*>(dout), dcls, B, (int64_t)(K + 1) * D, D);)
   PASSL_RETURN_IF_LAUNCH_FAILED();
   return PASSL_OK;
 }
@@ -793,10 +713,10 @@ extern "C" int passl_hip_mae_unshuffle(const void* x, const float* mask_token, c
   if (!x || !mask_token || !pos || !ids_restore || !out || B <= 0 || L <= 0 || K <= 0 || K > L ||
       D <= 0 || (D & 7))
     return PASSL_EINVAL;
-  VIT_DISPATCH(dtype, hipLaunchKernelGGL(mae_unshuffle_kernel<T>,
-                                         dim3(grid_for((int64_t)B * (L + 1) * (D >> 3))), dim3(kThreads), 0,
-                                         as_stream(stream), reinterpret_cast<const T*>(x), mask_token, pos,
-                                         ids_restore, reinterpret_cast<T*>(out), B, L, K, D);)
+  PASSL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(mae_unshuffle_kernel<T>,
+                                                 dim3(grid_for((int64_t)B * (L + 1) * (D >> 3))), dim3(kThreads), 0,
+                                                 as_stream(stream), reinterpret_cast<const T*>(x), mask_token, pos,
+                                                 ids_restore, reinterpret_cast<T*>(out), B, L, K, D);)
   PASSL_RETURN_IF_LAUNCH_FAILED();
   return PASSL_OK;
 }
@@ -818,10 +738,10 @@ extern "C" int passl_hip_mae_unshuffle_bwd(const void* dout, const int32_t* ids_
   const int tpb = (int)((ntok + slabs - 1) / slabs);
   slabs = (int)((ntok + tpb - 1) / tpb);
   if (ws_floats < (int64_t)slabs * D) return PASSL_EINVAL;
-  VIT_DISPATCH(dtype, hipLaunchKernelGGL(mae_unshuffle_bwd_kernel<T>, dim3((D + 255) / 256, slabs),
-                                         dim3(kThreads), 0, as_stream(stream),
-                                         reinterpret_cast<const T*>(dout), ids_keep, ids_restore,
-                                         reinterpret_cast<T*>(dx), ws, B, L, K, D, tpb);)
+  PASSL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(mae_unshuffle_bwd_kernel<T>, dim3((D + 255) / 256, slabs),
+                                                 dim3(kThreads), 0, as_stream(stream),
+                                                 reinterpret_cast<const T*>(dout), ids_keep, ids_restore,
+                                                 reinterpret_cast<T*>(dx), ws, B, L, K, D, tpb);)
   PASSL_RETURN_IF_LAUNCH_FAILED();
   return passl_slab_reduce_launch(ws, dmask_token, D, slabs, 1, as_stream(stream));
 }
@@ -830,9 +750,9 @@ extern "C" int passl_hip_patchify(const float* img, void* out, int B, int C, int
                                   int dtype, passl_stream_t stream) {
   if (!img || !out || B <= 0 || C <= 0 || p <= 0 || H <= 0 || W <= 0 || (H % p) || (W % p))
     return PASSL_EINVAL;
-  VIT_DISPATCH(dtype, hipLaunchKernelGGL(patchify_kernel<T>, dim3(grid_for((int64_t)B * C * H * W)),
-                                         dim3(kThreads), 0, as_stream(stream), img,
-                                         reinterpret_cast<T*>(out), B, C, H, W, p);)
+  PASSL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(patchify_kernel<T>, dim3(grid_for((int64_t)B * C * H * W)),
+                                                 dim3(kThreads), 0, as_stream(stream), img,
+                                                 reinterpret_cast<T*>(out), B, C, H, W, p);)
   PASSL_RETURN_IF_LAUNCH_FAILED();
   return PASSL_OK;
 }

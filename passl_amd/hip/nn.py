@@ -916,20 +916,24 @@ def drop_path_add(branch, residual, keep_row, keep_prob, B, T):
     return _DropPathAddFn.apply(branch, residual, keep_row, keep_prob, B, T)
 
 
-class _GeluFn(Function):
+class _UnaryFn(Function):
+    """A streaming activation: fwd(x) -> y and bwd(dy, x) -> dx are the op's two functions of ops."""
+
     @staticmethod
-    def forward(ctx, x):
+    def forward(ctx, x, fwd, bwd):
+        x = x.contiguous()              # saved as the kernels read it: dy arrives in the layout of y
         ctx.save_for_backward(x)
-        return ops.gelu_fwd(x.contiguous())
+        ctx.bwd = bwd
+        return fwd(x)
 
     @staticmethod
     def backward(ctx, dy):
         (x,) = ctx.saved_tensors
-        return ops.gelu_bwd(dy.contiguous(), x)
+        return ctx.bwd(dy.contiguous(), x), None, None
 
 
 def gelu(x):
-    return _GeluFn.apply(x)
+    return _UnaryFn.apply(x, ops.gelu_fwd, ops.gelu_bwd)
 
 
 class GELU(Layer):
@@ -937,21 +941,9 @@ class GELU(Layer):
         return gelu(x)
 
 
-class _TanhFn(Function):
-    @staticmethod
-    def forward(ctx, x):
-        ctx.save_for_backward(x)
-        return ops.tanh_fwd(x.contiguous())
-
-    @staticmethod
-    def backward(ctx, dy):
-        (x,) = ctx.saved_tensors
-        return ops.tanh_bwd(dy.contiguous(), x)
-
-
 class Tanh(Layer):
     def forward(self, x):
-        return _TanhFn.apply(x)
+        return _UnaryFn.apply(x, ops.tanh_fwd, ops.tanh_bwd)
 
 
 class _AttentionFn(Function):
@@ -996,23 +988,11 @@ def attention(qkv, B, T, H, DH, scale, causal=False):
     return _AttentionFn.apply(qkv, B, T, H, DH, float(scale), bool(causal))
 
 
-class _QuickGeluFn(Function):
-    @staticmethod
-    def forward(ctx, x):
-        ctx.save_for_backward(x)
-        return ops.quick_gelu_fwd(x.contiguous())
-
-    @staticmethod
-    def backward(ctx, dy):
-        (x,) = ctx.saved_tensors
-        return ops.quick_gelu_bwd(dy.contiguous(), x)
-
-
 class QuickGELU(Layer):
     """x * sigmoid(1.702 x) (passl_v110/modeling/backbones/base_transformer.py:25-28)."""
 
     def forward(self, x):
-        return _QuickGeluFn.apply(x)
+        return _UnaryFn.apply(x, ops.quick_gelu_fwd, ops.quick_gelu_bwd)
 
 
 class _GatherRowsFn(Function):

@@ -736,30 +736,28 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dgamma, dbeta, dres=None, defer_para
     return dx
 
 
+def _unary(name, x, dy=None):
+    """The streaming activations (csrc/eltwise.h): passl_hip_<name>(x, y, ...) or, with dy, (dy, x, dx, ...)."""
+    out = torch.empty_like(x)
+    args = (L.ptr(x), L.ptr(out)) if dy is None else (L.ptr(dy), L.ptr(x), L.ptr(out))
+    L.check(getattr(_lib(), 'passl_hip_' + name)(*args, x.numel(), L.dt(x), L.stream()), name)
+    return out
+
+
 def gelu_fwd(x):
-    y = torch.empty_like(x)
-    L.check(_lib().passl_hip_gelu_fwd(L.ptr(x), L.ptr(y), x.numel(), L.dt(x), L.stream()), 'gelu_fwd')
-    return y
+    return _unary('gelu_fwd', x)
 
 
 def gelu_bwd(dy, x):
-    dx = torch.empty_like(x)
-    L.check(_lib().passl_hip_gelu_bwd(L.ptr(dy), L.ptr(x), L.ptr(dx), x.numel(), L.dt(x), L.stream()),
-            'gelu_bwd')
-    return dx
+    return _unary('gelu_bwd', x, dy)
 
 
 def tanh_fwd(x):
-    y = torch.empty_like(x)
-    L.check(_lib().passl_hip_tanh_fwd(L.ptr(x), L.ptr(y), x.numel(), L.dt(x), L.stream()), 'tanh_fwd')
-    return y
+    return _unary('tanh_fwd', x)
 
 
 def tanh_bwd(dy, x):
-    dx = torch.empty_like(x)
-    L.check(_lib().passl_hip_tanh_bwd(L.ptr(dy), L.ptr(x), L.ptr(dx), x.numel(), L.dt(x), L.stream()),
-            'tanh_bwd')
-    return dx
+    return _unary('tanh_bwd', x, dy)
 
 
 # the envelope of csrc/attention.hip / attention_bf16.hip (shape_ok): model constructors check it up front
@@ -1226,17 +1224,11 @@ def adamw_groups_clip_dev(p, g, m, v, table, hyper, clip, b1, b2, eps, grad_scal
 
 # ------------------------------------------------------------------ CLIP
 def quick_gelu_fwd(x):
-    y = torch.empty_like(x)
-    L.check(_lib().passl_hip_quick_gelu_fwd(L.ptr(x), L.ptr(y), x.numel(), L.dt(x), L.stream()),
-            'quick_gelu_fwd')
-    return y
+    return _unary('quick_gelu_fwd', x)
 
 
 def quick_gelu_bwd(dy, x):
-    dx = torch.empty_like(x)
-    L.check(_lib().passl_hip_quick_gelu_bwd(L.ptr(dy), L.ptr(x), L.ptr(dx), x.numel(), L.dt(x), L.stream()),
-            'quick_gelu_bwd')
-    return dx
+    return _unary('quick_gelu_bwd', x, dy)
 
 
 def embed_fwd(text, table, pos, dtype):
