@@ -574,6 +574,22 @@ def test_asm_diff_reports_an_unchanged_stream_under_a_new_name_as_renamed():
     assert asm_diff.match({'x': ['a']}, {'x': ['b'], 'z': ['a']}) == (['x'], {}, [], ['z'])
 
 
+def test_asm_diff_pairs_a_removed_kernel_with_the_new_stream_nearest_in_order():
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, 'tools'))
+    import asm_diff
+    old = ['\tv_add a', '\tv_mul b', '\tv_mfma c', '\ts_nop 0', '\t.p2align 8', '\tv_sub d']
+    moved = ['\tv_mul b', '\tv_add a', '\tv_mfma c', '\ts_nop 0', '\t.p2align 8', '\tv_sub d']
+    # the same lines as `old` in another order throughout (a multiset comparison could not tell it from `moved`),
+    # and a stream with one instruction replaced
+    shuffled = ['\tv_sub d', '\t.p2align 8', '\ts_nop 0', '\tv_mfma c', '\tv_mul b', '\tv_add a']
+    edited = ['\tv_add a', '\tv_mul b', '\tv_mfma c', '\ts_nop 0', '\t.p2align 8', '\tv_max d', '\tv_max e', '\tv_max f']
+    name, lines, ops = asm_diff.closest(old, {'shuffled': shuffled, 'moved': moved, 'edited': edited})
+    assert (name, ops) == ('moved', {}) and lines == 2          # one line left its place and came back one later
+    name, lines, ops = asm_diff.closest(old, {'shuffled': shuffled, 'edited': edited})
+    assert name == 'edited' and lines == 3 and ops == {'v_max': 3, 'v_sub': -1}     # directives are not opcodes
+
+
 # ------------------------------------------------------------------ MAE / CLIP rows (host side)
 REF_MAE_CFG = '/root/reference/configs/mae/mae_vit_b_pretrain.yaml'
 REF_CLIP_CFG = '/root/reference/configs/clip/vit-b-32.yaml'

@@ -4,12 +4,16 @@ the working tree to gfx950 assembly (same flags as the build) and compares the i
 its instruction stream unchanged is reported as renamed, not as changed.  The compared stream runs to the end of the
 kernel's descriptor (kernarg size, register counts), and the offsets of the hidden arguments follow the explicit ones:
 a kernel folded into a template with another parameter list therefore comes out as removed + new, never as renamed.
+A removed kernel is shown next to the new kernel whose stream is closest to it, with the number of lines that differ and
+the opcodes whose counts changed: a rewrite that only moved instructions shows up as such.
 Runs without a GPU.
 
     python tools/asm_diff.py <commit>        # e.g. the last commit whose build passed the GPU suite
 
 Used to show that an opt-in kernel added next to the product kernels (a new template parameter with a default, a new
 kernel in the same file) left the product kernels' code bit-identical."""
+import collections
+import difflib
 import os
 import re
 import subprocess
@@ -61,6 +65,17 @@ def match(a, b):
     return diff, renamed, gone, [n for n in new if n not in renamed.values()]
 
 
+def closest(stream, new):
+    """(name, differing lines, {opcode: count change}) of the stream of `new` ({name: stream}) nearest to `stream`."""
+    def opcodes(x):
+        return collections.Counter(line.split()[0] for line in x if line.startswith('\t') and not line.lstrip().startswith('.'))
+    name = max(new, key=lambda k: difflib.SequenceMatcher(None, stream, new[k], autojunk=False).ratio())
+    ops = difflib.SequenceMatcher(None, stream, new[name], autojunk=False).get_opcodes()
+    lines = sum(max(i2 - i1, j2 - j1) for tag, i1, i2, j1, j2 in ops if tag != 'equal')
+    a, b = opcodes(stream), opcodes(new[name])
+    return name, lines, {o: b[o] - a[o] for o in sorted(set(a) | set(b)) if a[o] != b[o]}
+
+
 def demangle(name):
     return subprocess.run(['c++filt', name], capture_output=True, text=True).stdout.strip()[:140]
 
@@ -91,6 +106,10 @@ def main():
             for tag, names in (('different', diff), ('removed', gone), ('new', new)):
                 for n in names:
                     print('    %-9s %s' % (tag, demangle(n)))
+                    if tag == 'removed' and new:
+                        k, lines, ops = closest(a[n], {x: b[x] for x in new})
+                        print('              closest new: %s; %d of %d lines differ; opcode counts %s' % (
+                            demangle(k), lines, len(a[n]), ', '.join('%s %+d' % kv for kv in ops.items()) or 'equal'))
         print('# %s' % ('every kernel of the old build is unchanged' if changed == 0 else '%d kernels changed' % changed))
 
 
