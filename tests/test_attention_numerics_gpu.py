@@ -29,6 +29,7 @@ import pytest
 import torch
 
 import attention_util as A
+from guarded import Guarded
 
 pytestmark = pytest.mark.gpu
 
@@ -36,34 +37,7 @@ from passl_amd.hip import lib as L             # noqa: E402
 
 DEV = 'cuda'
 B, H = A.B, A.H
-GUARD_BYTES = 4096
-PATTERN = {2: 0x5A5A, 4: 0x5A5A5A5A}
 IDS = [A.case_id(c) for c in A.CASES]
-
-
-class Guarded:
-    """`numel` elements inside a larger device buffer, `skew` elements past a 16-byte boundary, with at least
-    GUARD_BYTES of a fixed bit pattern on either side."""
-
-    def __init__(self, numel, dtype, skew=0, fill=None):
-        size = torch.empty(0, dtype=dtype).element_size()
-        g = GUARD_BYTES // size
-        self.lo, self.hi, self.pattern = g + skew, g + skew + numel, PATTERN[size]
-        self.buf = torch.empty(self.hi + g, dtype=dtype, device=DEV)
-        self.bits = self.buf.view(torch.int16 if size == 2 else torch.int32)
-        self.bits.fill_(self.pattern)
-        self.view = self.buf[self.lo:self.hi]
-        assert self.buf.data_ptr() % 16 == 0 and self.view.data_ptr() % 16 == (skew * size) % 16
-        if fill is None:
-            self.view.fill_(float('nan'))
-        else:
-            self.view.copy_(fill.flatten().to(DEV).to(dtype))
-
-    def intact(self):
-        return bool((self.bits[:self.lo] == self.pattern).all()) and bool((self.bits[self.hi:] == self.pattern).all())
-
-    def raw(self):
-        return self.bits[self.lo:self.hi].clone()
 
 
 @pytest.fixture
