@@ -965,6 +965,39 @@ int passl_hip_cast_bf16_to_f32(const void* src, float* dst, int64_t n, passl_str
 int passl_hip_unpad_add(const float* src, float* dst, int64_t rows, int R, int dst_S, int dst_C, int src_S,
                         int src_C, passl_stream_t stream);
 
+/* ---- element-wise dropout (csrc/dropout.hip) ------------------------------------------------------------
+ * paddle.nn.Dropout(p), mode `upscale_in_train` [Paddle-semantics]: training out = kept ? x * factor : 0 with
+ * factor = float32(1 / (1 - float32(p))); evaluation is the identity and launches nothing.  Reference call sites:
+ * passl/models/vision_transformer.py Mlp :106-112, Attention :153-155, VisionTransformer pos_drop :358.
+ * The mask is defined by position: chunk k (elements 8k .. 8k+7) of the tensor at dropout site `site` takes
+ * Philox4x32-10 on counter (k, site, step_lo, step_hi), key (seed_lo, seed_hi) -> words x[0..3]; element e of the
+ * chunk is kept iff ((x[e >> 1] >> (16 * (e & 1))) & 0xFFFF) >= thr, thr = floor(p * 65536 + 0.5) in [0, 65535].
+ * `step` is a uint64 in device memory (8-byte aligned) that the launches READ; passl_hip_dropout_advance adds 1 to it
+ * (one thread), so a replayed step plan draws fresh masks with unchanged argument bytes.  n elements, a multiple of 8
+ * and at most 2^35 (PASSL_EUNSUPPORTED beyond); every tensor 16-byte aligned; fp32 arithmetic, one rounding to `dtype`.
+ *   dropout           out = mask * (in * factor)                  (applied to dy: the backward of every site)
+ *   dropout_add       out = residual + mask * (branch * factor)   (the product rounded to fp32 before the add)
+ *   gelu_dropout_fwd  out = mask * (gelu(x) * factor)
+ *   gelu_dropout_bwd  dx  = (mask * (dy * factor)) * gelu'(x) */
+int passl_hip_dropout_advance(int64_t* step, passl_stream_t stream);
+int passl_hip_dropout(const void* in, void* out, int64_t n, int thr, float factor, int64_t seed, const int64_t* step,
+                      int site, int dtype, passl_stream_t stream);
+int passl_hip_dropout_add(const void* branch, const void* residual, void* out, int64_t n, int thr, float factor,
+                          int64_t seed, const int64_t* step, int site, int dtype, passl_stream_t stream);
+int passl_hip_gelu_dropout_fwd(const void* x, void* out, int64_t n, int thr, float factor, int64_t seed,
+                               const int64_t* step, int site, int dtype, passl_stream_t stream);
+int passl_hip_gelu_dropout_bwd(const void* dy, const void* x, void* dx, int64_t n, int thr, float factor,
+                               int64_t seed, const int64_t* step, int site, int dtype, passl_stream_t stream);
+
+/* ViTCELoss(type='sigmoid'), passl/loss/celoss.py:58-95, over fp32 scores [N][C] and integer labels: the target is
+ * t_on at the label and t_off elsewhere (onehot * (1 - eps) + eps, rounded once by the caller).
+ *   fwd: out[0] = 1/N sum_i sum_c max(x, 0) - x t + log1p(exp(-|x|));  ws: N floats, row i's sum / N stays in ws[i]
+ *   bwd: dscores = (sigmoid(x) - t) * gloss[0] / N */
+int passl_hip_sigmoid_ce_fwd(const float* scores, const int64_t* labels, int N, int C, float t_on, float t_off,
+                             float* out, float* ws, int64_t ws_floats, passl_stream_t stream);
+int passl_hip_sigmoid_ce_bwd(const float* scores, const int64_t* labels, const float* gloss, int N, int C, float t_on,
+                             float t_off, float* dscores, passl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@
 //   forward_decoder :512-539            patchify/forward_loss :433-445,541-557
 #include "common.h"
 #include "eltwise.h"
+#include "gelu_op.h"
 
 namespace {
 
@@ -194,21 +195,10 @@ __global__ void __launch_bounds__(kThreads) ln_param_reduce_kernel(const float* 
   else dbeta[c2 - C] += a;
 }
 
-// ------------------------------------------------------------------ GELU (exact erf form)
-__device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
-__device__ __forceinline__ float gelu_grad_f(float x) {
-  const float cdf = 0.5f * (1.0f + erff(x * 0.70710678118654752f));
-  return cdf + x * 0.39894228040143268f * __expf(-0.5f * x * x);
-}
+// ------------------------------------------------------------------ GELU (exact erf form): GeluOp, gelu_op.h
 
-// operators of the streaming unary kernel (eltwise.h)
-struct GeluOp {
-  __device__ static __forceinline__ float fwd(float x) { return gelu_f(x); }
-  __device__ static __forceinline__ float grad(float x) { return gelu_grad_f(x); }
-};
-
-// tanh / its gradient (the `representation_size` head of the v2 VisionTransformer: tanh(head0(x)),
-// passl/models/vision_transformer.py:340-343)
+// tanh / its gradient, an operator of the streaming unary kernel as GeluOp is (the `representation_size` head of
+// the v2 VisionTransformer: tanh(head0(x)), passl/models/vision_transformer.py:340-343)
 struct TanhOp {
   __device__ static __forceinline__ float fwd(float x) { return tanhf(x); }
   __device__ static __forceinline__ float grad(float x) {

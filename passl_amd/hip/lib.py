@@ -202,6 +202,13 @@ SIGNATURES = {
     'passl_hip_prof_collect': (c_i, [c_i, C.POINTER(C.c_double), C.POINTER(c_l)]),
     'passl_hip_prof_collect_work': (c_i, [c_i, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     'passl_hip_prof_event_overhead': (c_i, [c_i, c_p, C.POINTER(C.c_double)]),
+    'passl_hip_dropout_advance': (c_i, [c_p, c_p]),
+    'passl_hip_dropout': (c_i, [c_p, c_p, c_l, c_i, c_f, c_l, c_p, c_i, c_i, c_p]),
+    'passl_hip_dropout_add': (c_i, [c_p, c_p, c_p, c_l, c_i, c_f, c_l, c_p, c_i, c_i, c_p]),
+    'passl_hip_gelu_dropout_fwd': (c_i, [c_p, c_p, c_l, c_i, c_f, c_l, c_p, c_i, c_i, c_p]),
+    'passl_hip_gelu_dropout_bwd': (c_i, [c_p, c_p, c_p, c_l, c_i, c_f, c_l, c_p, c_i, c_i, c_p]),
+    'passl_hip_sigmoid_ce_fwd': (c_i, [c_p, c_p, c_i, c_i, c_f, c_f, c_p, c_p, c_l, c_p]),
+    'passl_hip_sigmoid_ce_bwd': (c_i, [c_p, c_p, c_p, c_i, c_i, c_f, c_f, c_p, c_p]),
 }
 
 _lib = None

@@ -916,6 +916,137 @@ def drop_path_add(branch, residual, keep_row, keep_prob, B, T):
     return _DropPathAddFn.apply(branch, residual, keep_row, keep_prob, B, T)
 
 
+class DropoutState:
+    """What the dropout sites of ONE model share (csrc/dropout.hip): the rate as (thr, factor), the Philox key, the
+    step counter in device memory and the ordinal of the current training pass on the host.
+
+    ``begin_pass`` — once at the head of every training-mode forward — advances the device counter (one launch) and the
+    ordinal.  Every site of that pass, forward and backward, then reads the same counter value, so the backward
+    recomputes the forward's masks.  An autograd node remembers the ordinal it was made under; a backward under
+    another ordinal (two training forwards before a backward) would draw different masks and raises instead."""
+
+    def __init__(self, p, seed=0, step=0):
+        self.p = float(p)
+        self.thr, self.factor = ops.dropout_params(p)
+        self.ordinal = 0
+        self._step = None
+        self.set_seed(seed, step)
+
+    def set_seed(self, seed, step=0):
+        self.seed = int(seed) & ((1 << 64) - 1)
+        self.step0 = int(step) & ((1 << 64) - 1)
+        if self._step is not None:
+            self._step.fill_(self.step0 - (1 << 64) if self.step0 >= 1 << 63 else self.step0)
+
+    def step(self):
+        """The counter's value (reads the device: synchronises)."""
+        return self.step0 if self._step is None else int(self._step.item()) & ((1 << 64) - 1)
+
+    def begin_pass(self, device):
+        if self._step is None:
+            self._step = torch.zeros(1, dtype=torch.int64, device=device)
+            self.set_seed(self.seed, self.step0)
+        ops.dropout_advance(self._step)
+        self.ordinal += 1
+
+    def args(self, site):
+        if self._step is None:
+            raise RuntimeError('a dropout site ran before DropoutState.begin_pass: the step counter does not exist yet')
+        return self.thr, self.factor, self.seed, self._step, int(site)
+
+    def check(self, ordinal):
+        if ordinal != self.ordinal:
+            raise RuntimeError('dropout backward of training pass %d while the model is in pass %d: the step counter '
+                               'has moved, the masks would differ from the forward\'s (run each backward before the '
+                               'next training forward)' % (ordinal, self.ordinal))
+
+
+class _DropoutFn(Function):
+    """mask * (x * factor); the backward is the same launch on dy."""
+
+    @staticmethod
+    def forward(ctx, x, state, site):
+        ctx.state, ctx.site, ctx.ordinal = state, site, state.ordinal
+        return ops.dropout(x.contiguous(), *state.args(site))
+
+    @staticmethod
+    def backward(ctx, dy):
+        ctx.state.check(ctx.ordinal)
+        return ops.dropout(dy.contiguous(), *ctx.state.args(ctx.site)), None, None
+
+
+class _DropoutAddFn(Function):
+    """residual + mask * (branch * factor): the residual add of a block whose branch ends in a dropout.  Backward
+    returns (mask * (dy * factor), dy): the second goes back into LayerNorm.fork's ``dres`` as _DropPathAddFn's does."""
+
+    @staticmethod
+    def forward(ctx, branch, residual, state, site):
+        ctx.state, ctx.site, ctx.ordinal = state, site, state.ordinal
+        return ops.dropout_add(branch.contiguous(), residual.contiguous(), *state.args(site))
+
+    @staticmethod
+    def backward(ctx, dy):
+        ctx.state.check(ctx.ordinal)
+        dy = dy.contiguous()
+        return ops.dropout(dy, *ctx.state.args(ctx.site)), dy, None, None
+
+
+class _GeluDropoutFn(Function):
+    """mask * (gelu(x) * factor) in the GELU launch; backward (mask * (dy * factor)) * gelu'(x) in the GELU backward's."""
+
+    @staticmethod
+    def forward(ctx, x, state, site):
+        x = x.contiguous()
+        ctx.save_for_backward(x)
+        ctx.state, ctx.site, ctx.ordinal = state, site, state.ordinal
+        return ops.gelu_dropout_fwd(x, *state.args(site))
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        ctx.state.check(ctx.ordinal)
+        return ops.gelu_dropout_bwd(dy.contiguous(), x, *ctx.state.args(ctx.site)), None, None
+
+
+def dropout(x, state, site):
+    return _DropoutFn.apply(x, state, site)
+
+
+def dropout_add(branch, residual, state, site):
+    return _DropoutAddFn.apply(branch, residual, state, site)
+
+
+def gelu_dropout(x, state, site):
+    return _GeluDropoutFn.apply(x, state, site)
+
+
+class Dropout(Layer):
+    """paddle.nn.Dropout(p) in its default ``upscale_in_train`` mode [Paddle-semantics]: training
+    ``kept ? x / (1 - p) : 0``, evaluation the identity.  The mask is a function of (seed, step, site, position)
+    (csrc/dropout.hip); the owning model binds the layer to its DropoutState and a site number."""
+
+    def __init__(self, p=0.5, axis=None, mode='upscale_in_train', name=None):
+        super().__init__()
+        if mode != 'upscale_in_train':
+            raise NotImplementedError("Dropout(mode=%r): only 'upscale_in_train' is built" % (mode,))
+        if axis is not None:
+            raise NotImplementedError('Dropout(axis=...) is not built')
+        ops.dropout_params(p)                              # refuses a rate outside [0, 1)
+        self.p = float(p)
+        self.state = self.site = None
+
+    def bind(self, state, site):
+        self.state, self.site = state, int(site)
+        return self
+
+    def forward(self, x):
+        if not (self.training and self.p > 0.):
+            return x
+        if self.state is None:
+            raise RuntimeError('Dropout(p=%g) in training mode is not bound to a DropoutState / site' % self.p)
+        return dropout(x, self.state, self.site)
+
+
 class _UnaryFn(Function):
     """A streaming activation: fwd(x) -> y and bwd(dy, x) -> dx are the op's two functions of ops."""
 

@@ -6,6 +6,7 @@ kernels from libpassl_hip.so; host tensors are refused (lib.ptr raises).
 import ctypes as C
 import math
 
+import numpy as np
 import torch
 
 from . import config
@@ -865,6 +866,58 @@ def drop_path_bwd(dy, keep_row, keep_prob, B, T):
     return dbranch
 
 
+# ------------------------------------------------------------------ element-wise dropout (csrc/dropout.hip)
+def dropout_params(p):
+    """-> (thr, factor) of rate ``p``: thr = floor(p * 65536 + 0.5) in double, factor = float32(1 / (1 - float32(p)))
+    [Paddle-semantics: upscale_in_train].  p outside [0, 1), or one that rounds to thr = 65536, is refused."""
+    p = float(p)
+    thr = int(math.floor(p * 65536.0 + 0.5)) if 0.0 <= p < 1.0 else -1
+    if not 0 <= thr <= 65535:
+        raise ValueError('dropout rate must be in [0, 1) (threshold floor(p * 65536 + 0.5) in [0, 65535]), got %r' % p)
+    return thr, float(np.float32(1.0) / (np.float32(1.0) - np.float32(p)))
+
+
+def _signed64(v):
+    v &= (1 << 64) - 1
+    return v - (1 << 64) if v >= 1 << 63 else v          # the same 64-bit pattern as a signed argument
+
+
+def dropout_advance(step):
+    """step: device int64 [1]; one launch adds 1."""
+    L.check(_lib().passl_hip_dropout_advance(L.ptr(step), L.stream()), 'dropout_advance')
+    return step
+
+
+def _dropout(name, tensors, thr, factor, seed, step, site, out=None):
+    """The four launches of csrc/dropout.hip: passl_hip_<name>(*tensors, out, n, thr, factor, seed, step, site, ...)."""
+    x = tensors[0]
+    out = torch.empty_like(x) if out is None else out
+    L.check(getattr(_lib(), 'passl_hip_' + name)(*[L.ptr(t) for t in tensors], L.ptr(out), x.numel(), int(thr),
+                                                  float(factor), _signed64(int(seed)), L.ptr(step), int(site),
+                                                  L.dt(x), L.stream()), name)
+    return out
+
+
+def dropout(x, thr, factor, seed, step, site, out=None):
+    """mask * (x * factor); applied to dy it is the backward of every dropout site."""
+    return _dropout('dropout', (x,), thr, factor, seed, step, site, out)
+
+
+def dropout_add(branch, residual, thr, factor, seed, step, site, out=None):
+    """residual + mask * (branch * factor)."""
+    return _dropout('dropout_add', (branch, residual), thr, factor, seed, step, site, out)
+
+
+def gelu_dropout_fwd(x, thr, factor, seed, step, site, out=None):
+    """mask * (gelu(x) * factor)."""
+    return _dropout('gelu_dropout_fwd', (x,), thr, factor, seed, step, site, out)
+
+
+def gelu_dropout_bwd(dy, x, thr, factor, seed, step, site, out=None):
+    """(mask * (dy * factor)) * gelu'(x)."""
+    return _dropout('gelu_dropout_bwd', (dy, x), thr, factor, seed, step, site, out)
+
+
 # ------------------------------------------------------------------ mixup / cutmix, soft targets (csrc/mixup.hip)
 def batch_mix(x, lam, box=None):
     """Mixup._mix_batch on a resident fp32 NCHW batch, out of place (``x`` is not written); the partner of sample b is
@@ -1028,6 +1081,34 @@ def soft_ce_bwd(scores, target, lse, tsum, gloss):
     ds = torch.empty_like(scores)
     L.check(_lib().passl_hip_soft_ce_bwd(L.ptr(scores), L.ptr(target), L.ptr(lse), L.ptr(tsum), L.ptr(gloss), N, Cc,
                                          L.ptr(ds), L.stream()), 'soft_ce_bwd')
+    return ds
+
+
+def sigmoid_ce_targets(epsilon):
+    """(t_on, t_off) of ViTCELoss: onehot * (1 - eps) + eps at the label / elsewhere, in double, rounded once."""
+    if epsilon is None:
+        return 1.0, 0.0
+    eps = float(epsilon)
+    return float(np.float32(1.0 * (1.0 - eps) + eps)), float(np.float32(eps))
+
+
+def sigmoid_ce_fwd(scores, labels, t_on, t_off, rows=None):
+    """scores fp32 [N,C], labels int64 [N] -> out[1] = the mean over rows of the summed binary cross entropy with
+    logits.  ``rows``: an fp32 [N] buffer of the caller's that takes the place of the workspace (row i's sum / N)."""
+    assert scores.dtype == torch.float32 and labels.dtype == torch.int64
+    N, Cc = scores.shape
+    out = torch.empty(1, dtype=torch.float32, device=scores.device)
+    ws = workspace.get(N, scores.device) if rows is None else rows
+    L.check(_lib().passl_hip_sigmoid_ce_fwd(L.ptr(scores), L.ptr(labels), N, Cc, t_on, t_off, L.ptr(out), L.ptr(ws),
+                                            ws.numel(), L.stream()), 'sigmoid_ce_fwd')
+    return out
+
+
+def sigmoid_ce_bwd(scores, labels, gloss, t_on, t_off, out=None):
+    N, Cc = scores.shape
+    ds = torch.empty_like(scores) if out is None else out
+    L.check(_lib().passl_hip_sigmoid_ce_bwd(L.ptr(scores), L.ptr(labels), L.ptr(gloss), N, Cc, t_on, t_off, L.ptr(ds),
+                                            L.stream()), 'sigmoid_ce_bwd')
     return ds
 
 

@@ -8,9 +8,9 @@ from . import mae, moco, nt_xent
 from .moco import MoCoLoss, info_nce
 from .nt_xent import nt_xent as nt_xent_loss
 from .mae import masked_patch_loss
-from .celoss import CELoss
+from .celoss import CELoss, ViTCELoss
 
-_LOSSES = {'CELoss': CELoss}
+_LOSSES = {'CELoss': CELoss, 'ViTCELoss': ViTCELoss}
 
 
 class CombinedLoss(object):

@@ -13,7 +13,6 @@ The per-sample noise of random_masking comes from ``torch.rand`` on the device (
 tests inject the reference's draw); the argsort pair is replaced by a rank kernel.
 Stochastic depth of the fine-tuning ViT (``drop_path_rate``): one device-side Philox draw per forward pass fills a keep
 table, and the residual add of a block that can drop runs in csrc/drop_path.hip instead of the GEMM epilogue."""
-import os
 from functools import partial
 
 import torch
@@ -23,7 +22,8 @@ from torch.autograd import Function
 from ...hip import config, nn, ops
 from ...modules.get_sincos_pe import get_2d_sincos_pos_embed
 from ...modules.vit import (Attention, Block, Identity, Mlp, PatchEmbed, ViTTrunk, _TokensFn,      # noqa: F401
-                            alias_matrix_param, conv_default_normal_, to_2tuple, trunc_normal_, xavier_uniform_)
+                            alias_matrix_param, conv_default_normal_, process_rank, to_2tuple, trunc_normal_,
+                            xavier_uniform_)
 from .builder import BACKBONES
 
 
@@ -179,13 +179,6 @@ class _PatchMeanFn(Function):
         return dx.view(B * (L + 1), D), None, None, None
 
 
-def _process_rank():
-    import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized():
-        return dist.get_rank()
-    return int(os.environ.get('RANK', 0))
-
-
 class VisionTransformer(ViTTrunk):
     """The fine-tuning ViT of the v110 tree (passl_v110/modeling/backbones/mae.py:190-277): learnable ``cls_token`` /
     ``pos_embed`` (trunc-normal 0.02), pre-norm blocks, final LayerNorm, output = the class token's row.  Same kernels as
@@ -228,7 +221,7 @@ class VisionTransformer(ViTTrunk):
         self._dp_seed = self._dp_step0 = 0
         if self.drop_path_rate > 0.:
             seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
-            self.set_drop_path_seed(seed + _process_rank())
+            self.set_drop_path_seed(seed + process_rank())
         trunc_normal_(self.cls_token, std=0.02)
         trunc_normal_(self.pos_embed, std=0.02)
         with torch.no_grad():

@@ -35,6 +35,7 @@ class Transformer(nn.Layer):
                  norm_layer='nn.LayerNorm', epsilon=1e-5, **args):
         super().__init__()
         assert drop_path_rate == 0.0, 'stochastic depth is not used by the CLIP recipe'
+        assert drop_rate == 0.0, 'element-wise dropout is built for the v2 VisionTransformer only'
         self.embed_dim = embed_dim
         self.depth = depth
         self.blocks = tnn.ModuleList([

@@ -10,8 +10,9 @@ csrc/vit.hip; the classifier head works on fp32 rows.
 
 Envelope: what the fused attention kernel covers (sequence <= 208 tokens, head dim 32 or 64) — i.e. the 224-pixel
 base / large variants; the 384-pixel and 14-pixel-patch factories construct (names, shapes and state_dict are the
-reference's) and raise PASSL_EUNSUPPORTED when run.  Dropout / stochastic depth / ``qk_scale`` are not built (the
-pre-training recipes of tasks/ssl keep them at zero).
+reference's) and raise PASSL_EUNSUPPORTED when run.  ``drop_rate`` (the supervised ViT recipes set 0.1) is element-wise
+dropout at ``pos_drop`` and three sites per block (csrc/dropout.hip; masks by position from a seed and a device step
+counter); attention dropout / stochastic depth / ``qk_scale`` are not built (zero in every recipe).
 
 Initialisation [Paddle-semantics]: the reference relies on Paddle's defaults for the blocks' Linears (Xavier-uniform
 weights, zero bias) and the patch convolution (Normal(0, sqrt(2 / fan_in_of_the_filter))) and sets explicitly:
@@ -26,7 +27,7 @@ from ..hip import config
 from ..hip import nn as hnn
 from ..hip.nn import EncoderArena
 from ..modules.vit import (Attention, Block, Mlp, PatchEmbed, ViTTrunk, conv_default_normal_,      # noqa: F401
-                           to_2tuple, xavier_uniform_)                  # (the reference's names)
+                           process_rank as _process_rank, to_2tuple, xavier_uniform_)   # (the reference's names)
 from ..utils.checkpoint import load_lenient, read_pdparams, save_pdparams
 from .base_model import Model
 
@@ -45,9 +46,15 @@ class VisionTransformer(ViTTrunk, Model):
                  num_heads=12, mlp_ratio=4, qkv_bias=False, qk_scale=None, drop_rate=0., attn_drop_rate=0.,
                  drop_path_rate=0., norm_layer='nn.LayerNorm', epsilon=1e-5, representation_size=None, **kwargs):
         super().__init__()
-        if drop_rate or attn_drop_rate or drop_path_rate or qk_scale is not None:
-            raise NotImplementedError('dropout / stochastic depth / qk_scale are not built on the HIP path (zero in '
-                                      'the pre-training recipes)')
+        if attn_drop_rate or drop_path_rate or qk_scale is not None:
+            raise NotImplementedError('attention dropout / stochastic depth / qk_scale are not built on the HIP path '
+                                      '(zero in every v2 recipe)')
+        self.drop_rate = float(drop_rate)
+        if not 0. <= self.drop_rate < 1.:
+            raise ValueError('drop_rate must be in [0, 1), got %r' % (drop_rate,))
+        # seed, device step counter and pass ordinal of the 1 + 3 * depth dropout sites (plain attribute: not in
+        # state_dict(), not broadcast by param_sync); None without dropout
+        self._dropout = hnn.DropoutState(self.drop_rate) if self.drop_rate > 0. else None
         dev = config.get_device()
         self.class_num = class_num
         self.representation_size = representation_size
@@ -64,8 +71,12 @@ class VisionTransformer(ViTTrunk, Model):
         self.check_attention_envelope(img_size, patch_size, embed_dim, num_heads, num_patches + 1)
         self.pos_embed = tnn.Parameter(torch.zeros(1, num_patches + 1, embed_dim, device=dev))
         self.cls_token = tnn.Parameter(torch.zeros(1, 1, embed_dim, device=dev))
-        self.blocks = tnn.ModuleList([Block(embed_dim, num_heads, mlp_ratio, qkv_bias=qkv_bias, norm_layer=norm_layer)
-                                      for _ in range(depth)])
+        # site numbers: pos_drop 0; block i: 1 + 3i after proj, 2 + 3i after the activation, 3 + 3i after fc2
+        self.pos_drop = hnn.Dropout(self.drop_rate).bind(self._dropout, 0)
+        self.blocks = tnn.ModuleList([Block(embed_dim, num_heads, mlp_ratio, qkv_bias=qkv_bias, drop=self.drop_rate,
+                                            norm_layer=norm_layer) for _ in range(depth)])
+        for i, blk in enumerate(self.blocks):
+            blk.bind_dropout(self._dropout, 1 + 3 * i)
         self.norm = norm_layer(embed_dim)
         # classifier head
         if representation_size is not None:
@@ -90,10 +101,26 @@ class VisionTransformer(ViTTrunk, Model):
                 self.head.bias.zero_()
             self.pos_embed.copy_(torch.randn(self.pos_embed.shape) * 0.02)
             self.cls_token.zero_()
+        if self._dropout is not None:
+            # after the weights: a model with dropout initialises as one without; torch.manual_seed(seed + rank)
+            # reproduces a run and data-parallel ranks draw different masks (the convention of MAE_ViT's stochastic depth)
+            seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+            self.set_dropout_seed(seed + _process_rank())
         self.arena_q = EncoderArena(self, trainable=True)
 
     def sync_runtime_state(self):
         self.arena_q.refresh()
+
+    # ---- element-wise dropout
+    def set_dropout_seed(self, seed, step=0):
+        """Key of the Philox masks and the value of the step counter; the next training forward uses ``step + 1``."""
+        if self._dropout is None:
+            raise ValueError('set_dropout_seed needs a model built with drop_rate > 0')
+        self._dropout.set_seed(seed, step)
+
+    def dropout_step(self):
+        """The step counter = ``step`` of set_dropout_seed plus the training forwards since (reads the device)."""
+        return 0 if self._dropout is None else self._dropout.step()
 
     def load_state_dict(self, state_dict, strict=True):
         r = super().load_state_dict(state_dict, strict=strict)
@@ -101,7 +128,10 @@ class VisionTransformer(ViTTrunk, Model):
         return r
 
     def forward_features(self, x):
+        if self._dropout is not None and self.training:
+            self._dropout.begin_pass(x.device)               # one launch: every mask of this pass, fwd and bwd
         x, cls_rows, B, L = self.embed_tokens(x, self.cls_token, self.pos_embed)     # concat(cls, x) + pos_embed
+        x = self.pos_drop(x)
         return self.cls_features(self.run_blocks(x, B, L + 1), cls_rows, self.norm)
 
     def forward(self, x):

@@ -13,6 +13,7 @@ tensor equal to that matrix and becomes the kernels' causal flag; any other mask
 A tower keeps what really differs: parameter names and registration order, its init rule, sin-cos buffer versus
 learnable position table, its head.  ``ViTTrunk`` holds the steps they share."""
 import math
+import os
 
 import numpy as np
 import torch
@@ -24,6 +25,14 @@ from ..hip import config, nn, ops, plan as P
 
 def to_2tuple(x):
     return tuple([x] * 2)
+
+
+def process_rank():
+    """The rank that the seeds of stochastic depth and dropout are offset by: data-parallel ranks draw different masks."""
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized():
+        return dist.get_rank()
+    return int(os.environ.get('RANK', 0))
 
 
 class Identity(nn.Layer):
@@ -143,33 +152,66 @@ class PatchEmbed(nn.Layer):
         return self.norm(self.proj(rows))                    # [B*L, embed_dim]
 
 
+def _dropout_sites(layer, rate, sites, count):
+    """The (DropoutState, site, ...) a layer with a non-zero rate needs in training mode; no fall-back to 'no dropout'."""
+    if sites is None or len(sites) != 1 + count:
+        raise RuntimeError('%s with dropout rate %g in training mode needs a DropoutState and %d site number(s)'
+                           % (type(layer).__name__, rate, count))
+    return sites
+
+
+def _drop_or_add(y, residual, state, site):
+    return nn.dropout(y, state, site) if residual is None else nn.dropout_add(y, residual, state, site)
+
+
 class Mlp(nn.Layer):
+    """fc2(drop(act(fc1(x)))) then drop again (vision_transformer.py:106-112: one Dropout layer applied at two
+    places = two sites here).  With a rate, in training mode: the first dropout runs inside the GELU launch, the second
+    with the residual add in one launch after fc2, whose epilogue then adds nothing.  ``sites``: (state, site after the
+    activation, site after fc2)."""
+
     def __init__(self, in_features, hidden_features=None, out_features=None, act_layer=nn.GELU, drop=0.):
         super().__init__()
-        assert drop == 0., 'element-wise dropout is not built on the HIP path'
         out_features = out_features or in_features
         hidden_features = hidden_features or in_features
         self.fc1 = nn.Linear(in_features, hidden_features)
         self.act = act_layer()
         self.fc2 = nn.Linear(hidden_features, out_features)
+        self.drop = nn.Dropout(drop)
+        if self.drop.p > 0. and not isinstance(self.act, nn.GELU):
+            raise NotImplementedError('Mlp(drop=%g): the dropout after the activation is built into the GELU launch '
+                                      'only (csrc/dropout.hip), not %s' % (drop, type(self.act).__name__))
 
-    def forward(self, x, residual=None):
+    def forward(self, x, residual=None, sites=None):
+        if self.drop.p > 0. and self.training:
+            state, s_act, s_out = _dropout_sites(self, self.drop.p, sites, 2)
+            y = self.fc2(nn.gelu_dropout(self.fc1(x), state, s_act))
+            return _drop_or_add(y, residual, state, s_out)
         return self.fc2(self.act(self.fc1(x)), residual=residual)
 
 
 class Attention(nn.Layer):
+    """``proj_drop``: dropout after the output projection (vision_transformer.py:153-155); in training mode it runs
+    with the residual add in one launch after proj.  ``sites``: (state, site).  ``attn_drop`` would need the draw
+    inside the attention kernel and is not built."""
+
     def __init__(self, dim, num_heads=8, qkv_bias=False, qk_scale=None, attn_mask=None, attn_drop=0., proj_drop=0.):
         super().__init__()
-        assert attn_drop == 0. and proj_drop == 0.
+        if attn_drop != 0.:
+            raise NotImplementedError('attn_drop (dropout of the attention probabilities) is not built on the HIP path')
         self.num_heads = num_heads
         self.head_dim = dim // num_heads
         self.scale = qk_scale or self.head_dim ** -0.5
         self.qkv = nn.Linear(dim, dim * 3, bias_attr=None if qkv_bias else False)
         self.causal = _is_causal(attn_mask)
         self.proj = nn.Linear(dim, dim)
+        self.proj_drop = nn.Dropout(proj_drop)
 
-    def forward(self, x, B, T, residual=None):
+    def forward(self, x, B, T, residual=None, sites=None):
         a = nn.attention(self.qkv(x), B, T, self.num_heads, self.head_dim, self.scale, causal=self.causal)
+        if self.proj_drop.p > 0. and self.training:
+            state, site = _dropout_sites(self, self.proj_drop.p, sites, 1)
+            return _drop_or_add(self.proj(a), residual, state, site)
         return self.proj(a, residual=residual)
 
 
@@ -187,6 +229,13 @@ class Block(nn.Layer):
             raise ValueError('drop_path must be in [0, 1), got %r' % drop_path)
         self.drop_path = drop_path
         self.keep_prob = float(np.float32(1.0) - np.float32(drop_path))
+        # element-wise dropout after proj, after the activation and after fc2 (reference: proj_drop=drop, Mlp(drop=drop));
+        # the owning model binds its DropoutState and the first of the block's three site numbers
+        self.drop = float(drop)
+        self._drop_state, self._drop_site = None, 0
+        if self.drop > 0. and self.drop_path > 0.:
+            raise NotImplementedError('Block(drop=%g, drop_path=%g): dropout and stochastic depth in one block are not '
+                                      'built (no recipe sets both)' % (self.drop, self.drop_path))
         norm_layer = resolve_norm_layer(norm_layer)
         norm_kw = {} if epsilon is None else {'epsilon': epsilon}
         self.norm1 = norm_layer(dim, **norm_kw)
@@ -200,6 +249,8 @@ class Block(nn.Layer):
         # fork's gradient add inside the LayerNorm backward kernel (nn.LayerNorm.fork)
         if self.drop_path > 0. and self.training:
             return self._forward_drop_path(x, B, T, keep)
+        if self.drop > 0. and self.training:
+            return self._forward_dropout(x, B, T)
         h, xr = self.norm1.fork(x)
         x = self.attn(h, B, T, residual=xr)
         h, xr = self.norm2.fork(x)
@@ -215,6 +266,21 @@ class Block(nn.Layer):
         x = nn.drop_path_add(self.attn(h, B, T), xr, keep[0], self.keep_prob, B, T)
         h, xr = self.norm2.fork(x)
         return nn.drop_path_add(self.mlp(h), xr, keep[1], self.keep_prob, B, T)
+
+    def bind_dropout(self, state, first_site):
+        """Sites first_site (after proj), first_site + 1 (after the activation), first_site + 2 (after fc2)."""
+        self._drop_state, self._drop_site = state, int(first_site)
+
+    def _forward_dropout(self, x, B, T):
+        # x + drop(proj(.)) and x + drop(fc2(drop(act(.)))): the mask is per element, the epilogue's factors are per
+        # column, so — as under stochastic depth — proj / fc2 run without a residual and the add is the dropout launch
+        if self._drop_state is None:
+            raise RuntimeError('Block(drop=%g) in training mode is not bound to a DropoutState (bind_dropout)' % self.drop)
+        st, s = self._drop_state, self._drop_site
+        h, xr = self.norm1.fork(x)
+        x = self.attn(h, B, T, residual=xr, sites=(st, s))
+        h, xr = self.norm2.fork(x)
+        return self.mlp(h, residual=xr, sites=(st, s + 1, s + 2))
 
 
 class _TokensFn(Function):

@@ -192,3 +192,41 @@ class TimmCosine(LRScheduler):
 
     def __call__(self):
         return self.get_lr()
+
+
+@LRSCHEDULERS.register()
+class ViTLRScheduler(LRScheduler):
+    """passl/scheduler/lr_scheduler.py:80-118 (the supervised ViT / DeiT / MoCo-v3 fine-tuning recipes): linear
+    warm-up over ``warmup_steps`` optimizer steps multiplied onto a cosine (to 0) or linear (to ``linear_end``) decay
+    of the remaining ``T_max - warmup_steps``; ``T_max = epochs * step_each_epoch`` and a longer warm-up is cut to it.
+
+    Unlike TimmCosine the reference class does call the base __init__, which takes the first ``step()``
+    (``last_epoch`` 0, lr 0 under a warm-up).  ``warmup_steps >= T_max`` makes the progress 0 / 0 in the reference
+    (ZeroDivisionError) as soon as a value is asked for; here the decay is then over (progress 1), which is the limit of
+    the formula, and the warm-up factor alone shapes the rate.  ``__call__`` evaluates at the current ``last_epoch``
+    as the v2 optimizers do (see TimmCosine)."""
+
+    def __init__(self, learning_rate, step_each_epoch, epochs, decay_type='cosine', linear_end=1e-5, warmup_steps=0,
+                 verbose=False, last_epoch=-1, **kwargs):
+        if decay_type not in ('cosine', 'linear'):
+            raise ValueError("decay_type must be 'cosine' or 'linear', got %r" % (decay_type,))
+        self.linear_end = linear_end
+        self.T_max = epochs * step_each_epoch
+        self.warmup_steps = min(warmup_steps, self.T_max)
+        self.decay_type = decay_type
+        super().__init__(learning_rate, last_epoch, verbose)
+
+    def get_lr(self):
+        rest = self.T_max - self.warmup_steps
+        progress = (self.last_epoch - self.warmup_steps) / float(rest) if rest else 1.0
+        progress = min(1.0, max(0.0, progress))
+        if self.decay_type == 'linear':
+            lr = self.linear_end + (self.base_lr - self.linear_end) * (1.0 - progress)
+        else:
+            lr = 0.5 * self.base_lr * (1.0 + math.cos(math.pi * progress))
+        if self.warmup_steps:
+            lr = lr * min(1.0, self.last_epoch / self.warmup_steps)
+        return lr
+
+    def __call__(self):
+        return self.get_lr()
