@@ -670,6 +670,47 @@ int passl_hip_adamw_groups_clip_dev(float* p, const float* g, float* m, float* v
                                     const float* hyper, const float* clip, int n_sets, float beta1, float beta2,
                                     float epsilon, float grad_scale, passl_stream_t stream);
 
+/* ---------------------------------------------------------------- Adan (flat buffer)
+ * Reference: class Adan, passl/optimizer/adan.py:117-148 with is_vanilla=False (arXiv 2208.06677); replaces its
+ * per-parameter loop of framework element-wise ops by ONE launch over six flat fp32 vectors: p, m (exp_avg),
+ * d (exp_avg_diff), s (exp_avg_sq), pre (pre_grad) are updated from g, one float4 of each per lane:
+ *     gg   = g*grad_scale                       [clip variants: gg *= coef]
+ *     diff = first ? 0 : gg - pre
+ *     m    = b1*m + (1-b1)*gg;   d = b2*d + (1-b2)*diff;   u = gg + b2*diff;   s = b3*s + (1-b3)*u*u
+ *     den  = sqrt(s)/sqrt(1-b3^t) + eps;   upd = (m/(1-b1^t) + b2*d/(1-b2^t)) / den
+ *     p    = (p - lr*upd) / (1 + lr*wd)         [no_prox != 0: p = p*(1 - lr*wd) - lr*upd]
+ *     pre  = gg                                 (the scaled, clipped gradient, as the reference stores it)
+ * Every step-dependent scalar is read on the device: hyper = 8 floats {lr, b1^t, b2^t, b3^t, first (1.0 at t == 1,
+ * else 0.0), 0, 0, 0} — a recorded plan or a HIP graph replays correctly whichever step it was recorded at.  With
+ * first != 0 the contents of pre have no influence on any output (the reference creates pre_grad = grad.clone()).
+ * no_prox is configuration and travels by value.
+ *   passl_hip_adan_dev               one weight decay for the whole buffer.
+ *   passl_hip_adan_clip_dev          ... with the gradient times coef[0], a device float (passl_hip_grad_clip_finalize).
+ *   passl_hip_adan_groups_dev        a learning-rate multiplier and a weight decay per segment: the table of
+ *                                    passl_hip_adamw_groups_dev, unchanged (lr_s = hyper[0] * seg_lr_scale[s], one fp32
+ *                                    multiply, then exactly the flat update with (lr_s, seg_wd[s]): one shared device
+ *                                    function, so a segment gets the bits passl_hip_adan_dev gives that slice alone).
+ *   passl_hip_adan_groups_clip_dev   ... with the gradient of segment s times clip[2*seg_set[s] + 1]; seg_set[s] outside
+ *                                    [0, n_sets) (-1) means coefficient 1.
+ * The caller validates the tables' contents; the kernels keep every access inside [0, n) whatever they hold.  NULL
+ * pointers, n < 0, n % 4, n_seg <= 0, n_sets <= 0 (groups_clip), buffers not 16-byte aligned -> PASSL_EINVAL before
+ * any launch; n == 0 -> PASSL_OK without a launch. */
+int passl_hip_adan_dev(float* p, const float* g, float* m, float* d, float* s, float* pre, int64_t n,
+                       const float* hyper, float beta1, float beta2, float beta3, float epsilon, float weight_decay,
+                       int no_prox, float grad_scale, passl_stream_t stream);
+int passl_hip_adan_clip_dev(float* p, const float* g, float* m, float* d, float* s, float* pre, int64_t n,
+                            const float* hyper, const float* coef, float beta1, float beta2, float beta3, float epsilon,
+                            float weight_decay, int no_prox, float grad_scale, passl_stream_t stream);
+int passl_hip_adan_groups_dev(float* p, const float* g, float* m, float* d, float* s, float* pre, int64_t n,
+                              const int64_t* seg_end, const float* seg_lr_scale, const float* seg_wd, int n_seg,
+                              const float* hyper, float beta1, float beta2, float beta3, float epsilon, int no_prox,
+                              float grad_scale, passl_stream_t stream);
+int passl_hip_adan_groups_clip_dev(float* p, const float* g, float* m, float* d, float* s, float* pre, int64_t n,
+                                   const int64_t* seg_end, const float* seg_lr_scale, const float* seg_wd,
+                                   const int32_t* seg_set, int n_seg, const float* hyper, const float* clip, int n_sets,
+                                   float beta1, float beta2, float beta3, float epsilon, int no_prox, float grad_scale,
+                                   passl_stream_t stream);
+
 /* ---------------------------------------------------------------- stochastic depth
  * Reference: class DropPath / drop_path(), passl_v110/modeling/backbones/mae.py:32-50; the ladder
  * linspace(0, drop_path_rate, depth) :234; the two uses per Block :186-187.  Token rows [B*T][C] in `dtype`, sample b

@@ -309,11 +309,11 @@ class Engine(object):
         # fuse parameter storage — the arena IS fused storage, nothing to do.
         opt_cfg.pop('tensor_fusion', None)
         # grad_clip: {name: ClipGradByGlobalNorm, clip_norm: ...} builds the configuration object (core/grad_clip.py; name
-        # defaults to ClipGradByGlobalNorm, passl/optimizer/__init__.py:130-133) for AdamW, the one optimizer that clips
+        # defaults to ClipGradByGlobalNorm, passl/optimizer/__init__.py:130-133) for the two optimizers that clip
         grad_clip = opt_cfg.pop('grad_clip', None)
         if grad_clip not in (None, [], '', {}):
-            if klass is not OPTIMIZERS.get('AdamW'):
-                raise NotImplementedError('Optimizer.grad_clip is built for AdamW only, not for %s' % name)
+            if klass not in (OPTIMIZERS.get('AdamW'), OPTIMIZERS.get('Adan')):
+                raise NotImplementedError('Optimizer.grad_clip is built for Adan and AdamW only, not for %s' % name)
             opt_cfg['grad_clip'] = build_grad_clip(grad_clip)
         for k in ('no_weight_decay_name', 'layer_decay'):
             if opt_cfg.get(k, None) not in (None, [], ''):

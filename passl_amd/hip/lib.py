@@ -181,6 +181,13 @@ SIGNATURES = {
     'passl_hip_adamw_clip_dev': (c_i, [c_p, c_p, c_p, c_p, c_l, c_p, c_p, c_f, c_f, c_f, c_f, c_f, c_p]),
     'passl_hip_adamw_groups_clip_dev': (c_i, [c_p, c_p, c_p, c_p, c_l, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_f, c_f,
                                               c_f, c_f, c_p]),
+    'passl_hip_adan_dev': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_p, c_f, c_f, c_f, c_f, c_f, c_i, c_f, c_p]),
+    'passl_hip_adan_clip_dev': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_p, c_p, c_f, c_f, c_f, c_f, c_f, c_i, c_f,
+                                      c_p]),
+    'passl_hip_adan_groups_dev': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_p, c_p, c_p, c_i, c_p, c_f, c_f, c_f, c_f,
+                                        c_i, c_f, c_p]),
+    'passl_hip_adan_groups_clip_dev': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_i,
+                                             c_f, c_f, c_f, c_f, c_i, c_f, c_p]),
     'passl_hip_cosine_loss_fwd': (c_i, [c_p, c_p, c_i, c_i, c_f, c_p, c_p, c_p]),
     'passl_hip_cosine_loss_bwd': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p]),
     'passl_hip_softmax_ce_fwd': (c_i, [c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_l, c_p]),

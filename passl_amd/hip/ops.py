@@ -1303,6 +1303,59 @@ def adamw_groups_clip_dev(p, g, m, v, table, hyper, clip, b1, b2, eps, grad_scal
                                                    L.stream()), 'adamw_groups_clip_dev')
 
 
+# ---- Adan (include/passl_hip.h "Adan (flat buffer)"): p, m, d, s, pre from g; the tables are AdamW's
+ADAN_HYPER = 8      # floats of the device block {lr, b1^t, b2^t, b3^t, first, 0, 0, 0}
+
+
+def _adan_args(what, bufs, hyper, table=None):
+    """The six buffers hold the same number of elements and the hyper block its eight floats (the kernel reads
+    hyper[4]); a table covers exactly the buffer.  -> the device pointers of the buffers."""
+    n = bufs[0].numel()
+    if any(b.numel() != n for b in bufs):
+        raise ValueError('%s: buffers of %r elements (equal sizes wanted)' % (what, [b.numel() for b in bufs]))
+    if hyper.numel() < ADAN_HYPER:
+        raise ValueError('%s: the hyper block holds %d floats, %d wanted' % (what, hyper.numel(), ADAN_HYPER))
+    if table is not None and table['n'] != n:
+        raise ValueError('%s: the table covers %d elements, the buffer holds %d' % (what, table['n'], n))
+    return [L.ptr(b) for b in bufs]
+
+
+def adan_dev(p, g, m, d, s, pre, hyper, b1, b2, b3, eps, wd, no_prox=False, grad_scale=1.0):
+    """hyper: device float32 [lr, b1^t, b2^t, b3^t, first, 0, 0, 0], read when the kernel runs."""
+    ptrs = _adan_args('adan_dev', (p, g, m, d, s, pre), hyper)
+    L.check(_lib().passl_hip_adan_dev(*ptrs, p.numel(), L.ptr(hyper), b1, b2, b3, eps, wd, 1 if no_prox else 0,
+                                      grad_scale, L.stream()), 'adan_dev')
+
+
+def adan_clip_dev(p, g, m, d, s, pre, hyper, coef, b1, b2, b3, eps, wd, no_prox=False, grad_scale=1.0):
+    """adan_dev with the gradient times coef[0] (a device float, e.g. plan['out'][s, 1:]): gg = (g*grad_scale)*coef."""
+    ptrs = _adan_args('adan_clip_dev', (p, g, m, d, s, pre), hyper)
+    L.check(_lib().passl_hip_adan_clip_dev(*ptrs, p.numel(), L.ptr(hyper), L.ptr(coef), b1, b2, b3, eps, wd,
+                                           1 if no_prox else 0, grad_scale, L.stream()), 'adan_clip_dev')
+
+
+def adan_groups_dev(p, g, m, d, s, pre, table, hyper, b1, b2, b3, eps, no_prox=False, grad_scale=1.0):
+    """Adan with a learning-rate multiplier and a weight decay per segment (``table``: adamw_groups_table)."""
+    ptrs = _adan_args('adan_groups_dev', (p, g, m, d, s, pre), hyper, table)
+    L.check(_lib().passl_hip_adan_groups_dev(*ptrs, p.numel(), L.ptr(table['seg_end']), L.ptr(table['seg_lr_scale']),
+                                             L.ptr(table['seg_wd']), table['n_seg'], L.ptr(hyper), b1, b2, b3, eps,
+                                             1 if no_prox else 0, grad_scale, L.stream()), 'adan_groups_dev')
+
+
+def adan_groups_clip_dev(p, g, m, d, s, pre, table, hyper, clip, b1, b2, b3, eps, no_prox=False, grad_scale=1.0):
+    """adan_groups_dev with the gradient of segment s times clip[seg_set[s], 1] (``clip``: the [n_sets, 2] table of
+    grad_clip_finalize; ``table``: adamw_groups_clip_table)."""
+    if clip.numel() != 2 * table['n_sets']:
+        raise ValueError('adan_groups_clip_dev: the table names %d sets, the coefficient table holds %d'
+                         % (table['n_sets'], clip.numel() // 2))
+    ptrs = _adan_args('adan_groups_clip_dev', (p, g, m, d, s, pre), hyper, table)
+    L.check(_lib().passl_hip_adan_groups_clip_dev(*ptrs, p.numel(), L.ptr(table['seg_end']),
+                                                  L.ptr(table['seg_lr_scale']), L.ptr(table['seg_wd']),
+                                                  L.ptr(table['seg_set']), table['n_seg'], L.ptr(hyper), L.ptr(clip),
+                                                  table['n_sets'], b1, b2, b3, eps, 1 if no_prox else 0, grad_scale,
+                                                  L.stream()), 'adan_groups_clip_dev')
+
+
 # ------------------------------------------------------------------ CLIP
 def quick_gelu_fwd(x):
     return _unary('quick_gelu_fwd', x)

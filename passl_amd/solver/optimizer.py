@@ -49,12 +49,16 @@ class _DeviceHyper(object):
     ``push_hyper()`` = one host-side update of the step state (``_host_values``) + one asynchronous H2D copy from a
     ring of pinned slots (the host may run several steps ahead of the GPU: a slot is re-used only after the copy
     that read it has completed).  ``step()`` calls it itself unless the caller already did (graph replay: the copy
-    is stream-ordered in front of the graph launch, never part of the graph)."""
+    is stream-ordered in front of the graph launch, never part of the graph).
+
+    ``_HYPER_WIDTH``: the floats of the block (4; Adan's is 8 — a third beta power and its first-step flag).
+    ``_host_values`` returns the leading ones, the rest stays zero."""
 
     _RING = 16
+    _HYPER_WIDTH = 4
 
     def _init_hyper(self, device):
-        self._hyper_dev = torch.zeros(4, dtype=torch.float32, device=device)
+        self._hyper_dev = torch.zeros(self._HYPER_WIDTH, dtype=torch.float32, device=device)
         self._hyper_host = None
         self._hyper_ev = [None] * self._RING
         self._hyper_slot = 0
@@ -69,19 +73,21 @@ class _DeviceHyper(object):
         vals = self._host_values()
         if dev.is_cuda:
             if self._hyper_host is None:
-                self._hyper_host = torch.zeros(self._RING, 4, dtype=torch.float32).pin_memory()
+                self._hyper_host = torch.zeros(self._RING, self._HYPER_WIDTH, dtype=torch.float32).pin_memory()
             i = self._hyper_slot
             if self._hyper_ev[i] is not None:
                 self._hyper_ev[i].synchronize()          # the copy that read this slot RING steps ago is done
             h = self._hyper_host[i]
-            h[0], h[1], h[2] = vals
+            for k, x in enumerate(vals):
+                h[k] = x
             dev.copy_(h, non_blocking=True)
             ev = self._hyper_ev[i] or torch.cuda.Event()
             ev.record(torch.cuda.current_stream(dev.device))
             self._hyper_ev[i] = ev
             self._hyper_slot = (i + 1) % self._RING
         else:
-            dev[0], dev[1], dev[2] = vals
+            for k, x in enumerate(vals):
+                dev[k] = x
         self._hyper_pushed = True
 
     def set_lr(self, value):
@@ -418,12 +424,11 @@ def _flat_or_segments(param_slices, n_train, rows, sets):
     return None, (seg_end, seg_scale, seg_wd, None if sets is None else seg_set)
 
 
-@OPTIMIZERS.register()
-class AdamW(_ArenaOptimizer):
-    """paddle.optimizer.AdamW (registered by the reference at passl_v110/solver/optimizer.py:22) as ONE
-    launch over the flat arena.  adamw op  [Paddle-semantics]:
-        p *= 1 - lr*wd;  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;
-        p -= lr*sqrt(1-b2^t)/(1-b1^t) * m / (sqrt(v) + eps*sqrt(1-b2^t))
+class _GroupedArenaOptimizer(_ArenaOptimizer):
+    """An arena optimizer with ONE update launch per arena, parameter groups, global-norm clipping and a step count:
+    what AdamW and Adan share.  A subclass adds its ``_STATE``, its ``_host_values`` (which advances ``_t``) and its
+    ``_update``, the four launches of its rule.
+
     A float ``weight_decay`` decays EVERY trainable parameter (configs/mae/mae_vit_b_pretrain.yaml has no
     exclusion list; fixed sin-cos embeddings are buffers and are not touched).
 
@@ -434,35 +439,23 @@ class AdamW(_ArenaOptimizer):
     multiplies it; ``apply_decay_param_fun(name)`` — name = the Paddle auto-name (_paddle_auto_names) — switches the
     decay of a parameter off.  Every trainable parameter of an arena is listed exactly once.  The result is ONE table
     per arena (arena order, adjacent parameters with equal (multiplier, decay) merged; slot padding goes with the
-    parameter in front of it) for the grouped kernel (ops.adamw_groups_dev).  Multipliers all exactly 1.0 and decays
-    all equal = the flat kernel, launch for launch what a plain list gets.  The table is configuration, not state:
-    state_dict() holds the flat moments only.
+    parameter in front of it) for the grouped kernel (ops.adamw_groups_table: AdamW's and Adan's kernels read the same
+    table).  Multipliers all exactly 1.0 and decays all equal = the flat kernel, launch for launch what a plain list
+    gets.  The table is configuration, not state: state_dict() holds the flat state vectors and the step count ``t``.
 
     ``grad_clip`` (core.grad_clip.ClipGradByGlobalNorm): the clip set of a parameter joins (multiplier, decay) in the
     merge, and ``_update`` states the choice of launch per arena once — flat or grouped, each with or without the
     coefficient.  ``step`` with clipping: every arena's gradients complete, the chunk sums (one launch per arena), one
     finalize for all sets, then the updates.  Nothing comes back to the host: the coefficients are read by the update
     kernels from device memory."""
-    type = 'adamw'
-    _STATE = (('moment1', '_m'), ('moment2', '_v'))
 
-    def __init__(self, learning_rate=0.001, beta1=0.9, beta2=0.999, epsilon=1e-08, parameters=None,
-                 weight_decay=0.01, lr_ratio=None, apply_decay_param_fun=None, grad_clip=None,
-                 lazy_mode=False, multi_precision=False, name=None, betas=None, eps=None,
-                 use_master_param=None, exp_avg_force_fp32=None):
-        # v2 spelling (passl/optimizer/adamw.py:24-50, the MoCo-v3 yaml): betas=(b1, b2), eps.  use_master_param /
-        # exp_avg_force_fp32 ask for fp32 master weights and an fp32 first moment next to fp16 parameters: the
-        # flat arena IS fp32 (weights and both moments; the compute-dtype copy is derived from it every step), so
-        # both are always satisfied and the flags are accepted as no-ops.
-        if betas is not None:
-            beta1, beta2 = (float(b) for b in betas)
-        if eps is not None:
-            epsilon = eps
+    def _init_groups(self, learning_rate, parameters, weight_decay, grad_clip, lr_ratio=None,
+                     apply_decay_param_fun=None):
+        """Listed parameters -> rows -> runs -> launches -> device tables, and the clip plan over all arenas."""
         if grad_clip is not None and not isinstance(grad_clip, ClipGradByGlobalNorm):
             raise NotImplementedError('grad_clip: only core.grad_clip.ClipGradByGlobalNorm is built, got %r'
                                       % (type(grad_clip).__name__,))
         self._learning_rate = learning_rate
-        self._b1, self._b2, self._eps = float(beta1), float(beta2), float(epsilon)
         self._wd = float(weight_decay) if weight_decay else 0.0
         if self._wd < 0:
             raise ValueError('weight_decay must be >= 0, got %r' % (weight_decay,))
@@ -514,24 +507,9 @@ class AdamW(_ArenaOptimizer):
         Paddle auto-name ``apply_decay_param_fun`` was asked about."""
         return [row for rows in self._param_table for row in rows]
 
-    def _host_values(self):
-        self._t += 1
-        return self.get_lr(), self._b1 ** self._t, self._b2 ** self._t
-
     def _update(self, i, hyper):
         """The update launch of arena i: flat or grouped, each with or without a clip coefficient."""
-        a, m, v, table, coef = self._arenas[i], self._m[i], self._v[i], self._tables[i], self._clip_coef[i]
-        p = a.flat[:a.n_train]
-        if table is None and coef is None:
-            ops.adamw_dev(p, a.grads, m, v, hyper, self._b1, self._b2, self._eps, self._flat_wd[i], self.grad_scale)
-        elif table is None:
-            ops.adamw_clip_dev(p, a.grads, m, v, hyper, coef, self._b1, self._b2, self._eps, self._flat_wd[i],
-                               self.grad_scale)
-        elif 'seg_set' not in table:
-            ops.adamw_groups_dev(p, a.grads, m, v, table, hyper, self._b1, self._b2, self._eps, self.grad_scale)
-        else:
-            ops.adamw_groups_clip_dev(p, a.grads, m, v, table, hyper, self._clip['out'], self._b1, self._b2, self._eps,
-                                      self.grad_scale)
+        raise NotImplementedError
 
     @torch.no_grad()
     def step(self):
@@ -566,3 +544,106 @@ class AdamW(_ArenaOptimizer):
     def set_state_dict(self, sd):
         self._t = int(sd['t'])
         super().set_state_dict(sd)
+
+
+@OPTIMIZERS.register()
+class AdamW(_GroupedArenaOptimizer):
+    """paddle.optimizer.AdamW (registered by the reference at passl_v110/solver/optimizer.py:22) as ONE
+    launch over the flat arena.  adamw op  [Paddle-semantics]:
+        p *= 1 - lr*wd;  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;
+        p -= lr*sqrt(1-b2^t)/(1-b1^t) * m / (sqrt(v) + eps*sqrt(1-b2^t))
+    Groups, ``lr_ratio`` / ``apply_decay_param_fun`` and ``grad_clip``: _GroupedArenaOptimizer."""
+    type = 'adamw'
+    _STATE = (('moment1', '_m'), ('moment2', '_v'))
+
+    def __init__(self, learning_rate=0.001, beta1=0.9, beta2=0.999, epsilon=1e-08, parameters=None,
+                 weight_decay=0.01, lr_ratio=None, apply_decay_param_fun=None, grad_clip=None,
+                 lazy_mode=False, multi_precision=False, name=None, betas=None, eps=None,
+                 use_master_param=None, exp_avg_force_fp32=None):
+        # v2 spelling (passl/optimizer/adamw.py:24-50, the MoCo-v3 yaml): betas=(b1, b2), eps.  use_master_param /
+        # exp_avg_force_fp32 ask for fp32 master weights and an fp32 first moment next to fp16 parameters: the
+        # flat arena IS fp32 (weights and both moments; the compute-dtype copy is derived from it every step), so
+        # both are always satisfied and the flags are accepted as no-ops.
+        if betas is not None:
+            beta1, beta2 = (float(b) for b in betas)
+        if eps is not None:
+            epsilon = eps
+        self._b1, self._b2, self._eps = float(beta1), float(beta2), float(epsilon)
+        self._init_groups(learning_rate, parameters, weight_decay, grad_clip, lr_ratio, apply_decay_param_fun)
+
+    def _host_values(self):
+        self._t += 1
+        return self.get_lr(), self._b1 ** self._t, self._b2 ** self._t
+
+    def _update(self, i, hyper):
+        a, m, v, table, coef = self._arenas[i], self._m[i], self._v[i], self._tables[i], self._clip_coef[i]
+        p = a.flat[:a.n_train]
+        if table is None and coef is None:
+            ops.adamw_dev(p, a.grads, m, v, hyper, self._b1, self._b2, self._eps, self._flat_wd[i], self.grad_scale)
+        elif table is None:
+            ops.adamw_clip_dev(p, a.grads, m, v, hyper, coef, self._b1, self._b2, self._eps, self._flat_wd[i],
+                               self.grad_scale)
+        elif 'seg_set' not in table:
+            ops.adamw_groups_dev(p, a.grads, m, v, table, hyper, self._b1, self._b2, self._eps, self.grad_scale)
+        else:
+            ops.adamw_groups_clip_dev(p, a.grads, m, v, table, hyper, self._clip['out'], self._b1, self._b2, self._eps,
+                                      self.grad_scale)
+
+
+@OPTIMIZERS.register()
+class Adan(_GroupedArenaOptimizer):
+    """passl/optimizer/adan.py (arXiv 2208.06677; the optimizer of the reference's
+    ViT_base_patch16_224_in1k_adan_1n8c_dp_fp16o2.yaml) as ONE launch over the flat arena and four flat state vectors
+    (csrc/adan.hip), where the reference issues some twenty element-wise ops per parameter.  With gg the scaled,
+    clipped gradient (adan.py:117-148, is_vanilla=False):
+        diff = gg - pre_grad  (0 at t == 1);  m = b1 m + (1-b1) gg;  d = b2 d + (1-b2) diff;
+        u = gg + b2 diff;  s = b3 s + (1-b3) u^2;  upd = (m/(1-b1^t) + b2 d/(1-b2^t)) / (sqrt(s)/sqrt(1-b3^t) + eps)
+        p = (p - lr upd) / (1 + lr wd)        [no_prox: p = p (1 - lr wd) - lr upd];   pre_grad = gg
+    The hyper block is 8 floats {lr, b1^t, b2^t, b3^t, first, 0, 0, 0}.  ``first`` (1.0 at t == 1) stands for the
+    reference creating its state with pre_grad = grad.clone(); it is read on the device like the rate, so a step plan
+    recorded at t == 1 replays correctly at t >= 2 — and a run resumed from a state_dict (t >= 1) never takes the
+    first-step branch again.  ``param.grad`` keeps the unclipped gradient.
+    Groups and ``grad_clip``: _GroupedArenaOptimizer.  ``use_master_param``: the arena IS fp32, a no-op.  Refused:
+    ``is_vanilla`` (another state set; no recipe uses it) and ``lr_func`` groups."""
+    type = 'adan'
+    _STATE = (('exp_avg', '_m'), ('exp_avg_diff', '_d'), ('exp_avg_sq', '_s'), ('pre_grad', '_pre'))
+    _HYPER_WIDTH = 8
+
+    def __init__(self, learning_rate=1e-3, betas=(0.98, 0.92, 0.99), eps=1e-8, weight_decay=0.0, no_prox=False,
+                 grad_clip=None, use_master_param=None, is_vanilla=False, lr_func=None, parameters=None, lr=None):
+        if lr is not None:
+            learning_rate = lr
+        if is_vanilla:
+            raise NotImplementedError('Adan(is_vanilla=True) keeps another state set and is used by no recipe')
+        if lr_func is not None:
+            raise NotImplementedError('Adan(lr_func=...): LRCallable groups are not built')
+        betas = tuple(float(b) for b in betas)
+        if len(betas) != 3:
+            raise ValueError('Adan takes three betas, got %r' % (betas,))
+        if not 0.0 <= eps:                                       # adan.py:59-66
+            raise ValueError('Invalid epsilon value: {}'.format(eps))
+        for k, b in enumerate(betas):
+            if not 0.0 <= b < 1.0:
+                raise ValueError('Invalid beta parameter at index {}: {}'.format(k, b))
+        self._b1, self._b2, self._b3 = betas
+        self._eps = float(eps)
+        self._no_prox = bool(no_prox)
+        self._init_groups(learning_rate, parameters, weight_decay, grad_clip)
+
+    def _host_values(self):
+        self._t += 1
+        t = self._t
+        return self.get_lr(), self._b1 ** t, self._b2 ** t, self._b3 ** t, 1.0 if t == 1 else 0.0
+
+    def _update(self, i, hyper):
+        a, table, coef = self._arenas[i], self._tables[i], self._clip_coef[i]
+        bufs = (a.flat[:a.n_train], a.grads, self._m[i], self._d[i], self._s[i], self._pre[i])
+        cfg = (self._b1, self._b2, self._b3, self._eps)
+        if table is None and coef is None:
+            ops.adan_dev(*bufs, hyper, *cfg, self._flat_wd[i], self._no_prox, self.grad_scale)
+        elif table is None:
+            ops.adan_clip_dev(*bufs, hyper, coef, *cfg, self._flat_wd[i], self._no_prox, self.grad_scale)
+        elif 'seg_set' not in table:
+            ops.adan_groups_dev(*bufs, table, hyper, *cfg, self._no_prox, self.grad_scale)
+        else:
+            ops.adan_groups_clip_dev(*bufs, table, hyper, self._clip['out'], *cfg, self._no_prox, self.grad_scale)
