@@ -3,7 +3,7 @@
 A kernel that stores past the end of a fresh torch tensor corrupts whatever the caching allocator placed next to it,
 silently.  A `Guarded` payload lies inside a larger buffer whose margins hold a fixed bit pattern: `intact()` says
 whether both margins survived, and the payload starts out as NaN (floating types) or 0xA5 bytes (`prefill='a5'`,
-always for uint8), so that an element a kernel never wrote can be told from one it did.
+always for integer types), so that an element a kernel never wrote can be told from one it did.
 """
 import torch
 
@@ -16,8 +16,9 @@ _BITS = {1: torch.int8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
 
 class Guarded:
     """`numel` elements inside a larger device buffer, `skew` elements past a 16-byte boundary, with at least
-    GUARD_BYTES of a fixed bit pattern on either side.  dtype: bfloat16, float32, float64 or uint8.  The payload
-    holds `fill` when given, else NaN, else (uint8, or prefill='a5') bytes of 0xA5."""
+    GUARD_BYTES of a fixed bit pattern on either side.  dtype: bfloat16, float32, float64, uint8, int32 or
+    int64 (labels, indices).  The payload holds `fill` when given, else NaN, else (integer types, or prefill='a5')
+    bytes of 0xA5."""
 
     def __init__(self, numel, dtype, skew=0, fill=None, prefill=None):
         size = torch.empty(0, dtype=dtype).element_size()
