@@ -736,6 +736,60 @@ int passl_hip_drop_path_add(const void* branch, const void* residual, const floa
 int passl_hip_drop_path_bwd(const void* dy, const float* keep, float keep_prob, void* dbranch, int B, int T, int C,
                             int dtype, passl_stream_t stream);
 
+/* ---------------------------------------------------------------- ConvNeXt block: depthwise 7x7, layer scale
+ * Reference: class Block, passl/models/convnext.py:68-103: `self.dwconv = nn.Conv2D(dim, dim, 7, padding=3, groups=dim)`
+ * and the tail `x = input + self.drop_path(self.gamma * x)` :100-102.  x, y, dy, dx, add are NHWC [N][H][W][C] in
+ * `dtype`; w is fp32 in the parameter's own layout [C][1][7][7] (49 * C floats, read as it lies), bias fp32 [C].
+ * C % 8 == 0, every pointer 16-byte aligned, any H, W >= 1.  fp32 accumulation, one rounding to `dtype` at the store;
+ * no floating-point atomics: every result is bit-reproducible from launch to launch.
+ * NULL pointers (but `add` / `keep`, which may be NULL), sizes <= 0, C % 8, misalignment, a short workspace ->
+ * PASSL_EINVAL; an unknown dtype or a grid beyond 2^31 workgroups -> PASSL_EUNSUPPORTED. */
+
+/* y[n,p,q,c] = bias[c] + sum_{r,s} x[n,p+r-3,q+s-3,c] * w[c,0,r,s], zero padding. */
+int passl_hip_dwconv7_fwd(const void* x, const float* w, const float* bias, void* y, int N, int H, int W, int C,
+                          int dtype, passl_stream_t stream);
+/* dx[n,h,w,c] = add[n,h,w,c] + sum_{r,s} dy[n,h+3-r,w+3-s,c] * w[c,0,r,s].  add (may be NULL) is the gradient that
+ * arrives over the block's residual fork: it is added in fp32 before the single rounding. */
+int passl_hip_dwconv7_bwd_data(const void* dy, const float* w, const void* add, void* dx, int N, int H, int W, int C,
+                               int dtype, passl_stream_t stream);
+/* dw[c,0,r,s] = sum_{n,p,q} dy[n,p,q,c] * x[n,p+r-3,q+s-3,c] and dbias[c] = sum dy, WRITTEN (not accumulated) in fp32.
+ * Every workgroup leaves its sums in a slab of ws and a second and third launch add the slabs in ascending order.
+ * ws_floats >= PASSL_DWCONV7_WGRAD_WS_FLOATS(N, H, W, C). */
+#define PASSL_DWCONV7_WGRAD_TILE_H 8
+#define PASSL_DWCONV7_WGRAD_TILE_W 16
+#define PASSL_DWCONV7_WGRAD_MAX_SLABS 512
+#define PASSL_DWCONV7_WGRAD_TILES(N, H, W)                                                  \
+  ((int64_t)(N) * (((H) + PASSL_DWCONV7_WGRAD_TILE_H - 1) / PASSL_DWCONV7_WGRAD_TILE_H) *   \
+   (((W) + PASSL_DWCONV7_WGRAD_TILE_W - 1) / PASSL_DWCONV7_WGRAD_TILE_W))
+#define PASSL_DWCONV7_WGRAD_SLABS(N, H, W)                                        \
+  (PASSL_DWCONV7_WGRAD_TILES(N, H, W) < PASSL_DWCONV7_WGRAD_MAX_SLABS             \
+       ? PASSL_DWCONV7_WGRAD_TILES(N, H, W) : (int64_t)PASSL_DWCONV7_WGRAD_MAX_SLABS)
+#define PASSL_DWCONV7_WGRAD_WS_FLOATS(N, H, W, C) (PASSL_DWCONV7_WGRAD_SLABS(N, H, W) * 50 * (C))
+int passl_hip_dwconv7_bwd_weight(const void* x, const void* dy, float* dw, float* dbias, float* ws, int64_t ws_floats,
+                                 int N, int H, int W, int C, int dtype, passl_stream_t stream);
+
+/* Rows [B*T][C] in `dtype`, sample b owns rows b*T .. (b+1)*T-1; gamma fp32 [C]; keep one row [B] of the table
+ * passl_hip_drop_path_draw writes, or NULL (rate 0, evaluation), and then keep_prob is not read.
+ * out = residual + keep[b] * ((gamma[c] * branch) / keep_prob): four fp32 operations in the reference's order (`gamma * x`
+ * :100, `x.divide(keep_prob) * random_tensor`, `input + ...`), each rounded, none contracted into an fma, then one
+ * rounding to `dtype`.  keep == NULL: out = residual + gamma[c] * branch.  Rows of a dropped sample are copied from
+ * residual, branch is not read for them.  0 < keep_prob <= 1 when keep is given. */
+int passl_hip_layer_scale_add_fwd(const void* branch, const void* residual, const float* gamma, const float* keep,
+                                  float keep_prob, void* out, int B, int T, int C, int dtype, passl_stream_t stream);
+/* With g = keep[b] * (dy / keep_prob) (g = dy when keep == NULL): dbranch = gamma[c] * g (zeros for a dropped sample,
+ * dy and branch not read) and dgamma[c] = sum_rows branch * g, WRITTEN in fp32: one slab of ws per workgroup, added in
+ * ascending order by a second launch.  The residual's gradient is dy itself.  C <= PASSL_LAYER_SCALE_MAX_C;
+ * ws_floats >= PASSL_LAYER_SCALE_BWD_WS_FLOATS(B * T, C). */
+#define PASSL_LAYER_SCALE_MAX_C 8192
+#define PASSL_LAYER_SCALE_MAX_SLABS 1024
+#define PASSL_LAYER_SCALE_ROWS_PER_SLAB(M) \
+  (((int64_t)(M) + PASSL_LAYER_SCALE_MAX_SLABS - 1) / PASSL_LAYER_SCALE_MAX_SLABS)
+#define PASSL_LAYER_SCALE_BWD_WS_FLOATS(M, C) \
+  ((((int64_t)(M) + PASSL_LAYER_SCALE_ROWS_PER_SLAB(M) - 1) / PASSL_LAYER_SCALE_ROWS_PER_SLAB(M)) * (C))
+int passl_hip_layer_scale_add_bwd(const void* dy, const void* branch, const float* gamma, const float* keep,
+                                  float keep_prob, void* dbranch, float* dgamma, float* ws, int64_t ws_floats, int B,
+                                  int T, int C, int dtype, passl_stream_t stream);
+
 /* ---------------------------------------------------------------- mixup / cutmix and soft-target cross-entropy
  * Reference: class Mixup, passl_v110/datasets/preprocess/mixup.py:108-276 (the reference mixes on the host, in numpy or
  * through the framework's CPU tensors); SoftTargetCrossEntropy, tasks/ssl/mae/util/loss.py:44-47. */

@@ -162,6 +162,11 @@ SIGNATURES = {
     'passl_hip_drop_path_draw': (c_i, [c_p, c_p, c_i, c_i, c_l, c_p, c_p]),
     'passl_hip_drop_path_add': (c_i, [c_p, c_p, c_p, c_f, c_p, c_i, c_i, c_i, c_i, c_p]),
     'passl_hip_drop_path_bwd': (c_i, [c_p, c_p, c_f, c_p, c_i, c_i, c_i, c_i, c_p]),
+    'passl_hip_dwconv7_fwd': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
+    'passl_hip_dwconv7_bwd_data': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
+    'passl_hip_dwconv7_bwd_weight': (c_i, [c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_i, c_p]),
+    'passl_hip_layer_scale_add_fwd': (c_i, [c_p, c_p, c_p, c_p, c_f, c_p, c_i, c_i, c_i, c_i, c_p]),
+    'passl_hip_layer_scale_add_bwd': (c_i, [c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_p]),
     'passl_hip_batch_mix': (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_p]),
     'passl_hip_mixup_target': (c_i, [c_p, c_p, c_i, c_i, c_f, c_f, c_p]),
     'passl_hip_soft_ce_fwd': (c_i, [c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_l, c_p]),

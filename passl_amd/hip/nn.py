@@ -916,6 +916,205 @@ def drop_path_add(branch, residual, keep_row, keep_prob, B, T):
     return _DropPathAddFn.apply(branch, residual, keep_row, keep_prob, B, T)
 
 
+# =============================================================================== ConvNeXt pieces (csrc/dwconv.hip)
+def _need_contiguous(who, **tensors):
+    """A silent ``.contiguous()`` of a strided operand is a framework copy launch inside the step (foreign to a strict
+    step plan): the ConvNeXt layers refuse such an operand by name instead."""
+    for name, t in tensors.items():
+        if not t.is_contiguous():
+            raise ValueError('%s: %s must be contiguous (shape %s, strides %s)'
+                             % (who, name, tuple(t.shape), tuple(t.stride())))
+
+
+class _DepthwiseConvFn(Function):
+    """Depthwise 7x7 over NHWC.  add_slot: the GradSlot into which the block's tail (layer_scale_add) puts the gradient
+    of the residual fork `input + ...`; the data-gradient kernel adds it before its single rounding, so the fork costs
+    no separate add launch.  dW and dbias are WRITTEN straight into the arena's gradient slices, on the side stream when
+    there is one (they feed only the optimizer)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, layer, add_slot):
+        _need_contiguous('DepthwiseConv2D', x=x)
+        y = ops.dwconv7_fwd(x, weight.detach(), bias.detach())
+        if layer._rt is not None and any(ctx.needs_input_grad):
+            layer._rt.arena.expect_grad(layer._rt.indices)
+        if add_slot is not None and ctx.needs_input_grad[0]:
+            add_slot.arm()
+        ctx.save_for_backward(x)
+        ctx.layer, ctx.add_slot = layer, add_slot
+        ctx.side = streams.enabled(x)              # latched for the backward (see _ConvFn)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        layer = ctx.layer
+        dy = dy.contiguous()
+        for p in (layer.weight, layer.bias):
+            if p.grad is None:
+                p.grad = ops.zeros(*p.shape, dtype=p.dtype, device=p.device)      # (outside an arena; a library fill)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            add = ctx.add_slot.take() if ctx.add_slot is not None else None
+            dx = ops.dwconv7_bwd_data(dy, layer.weight.detach(), add)
+        dw, db = layer.weight.grad, layer.bias.grad
+        if ctx.side:
+            streams.side_later(dy.device, lambda: ops.dwconv7_bwd_weight_into(x, dy, dw, db), reads=(x, dy))
+        else:
+            ops.dwconv7_bwd_weight_into(x, dy, dw, db)
+        if layer._rt is not None:
+            layer._rt.arena.grad_ready(layer._rt.indices)
+        return dx, None, None, None, None
+
+
+class DepthwiseConv2D(Layer):
+    """paddle.nn.Conv2D(dim, dim, kernel_size=7, padding=3, groups=dim) over NHWC activations: parameters
+    ``weight [dim, 1, 7, 7]`` and ``bias [dim]`` in the reference's layout, read by the kernels as they lie."""
+
+    def __init__(self, dim, kernel_size=7, padding=3):
+        super().__init__()
+        if kernel_size != 7:
+            raise NotImplementedError('DepthwiseConv2D: kernel_size %r (the HIP kernels are 7x7)' % (kernel_size,))
+        if padding != 3:
+            raise NotImplementedError('DepthwiseConv2D: padding %r (the HIP kernels pad by 3)' % (padding,))
+        if dim <= 0 or dim % 8:
+            raise NotImplementedError('DepthwiseConv2D: dim %r is not a positive multiple of 8' % (dim,))
+        dev = config.get_device()
+        self.dim = dim
+        self.weight = tnn.Parameter(torch.empty(dim, 1, 7, 7, device=dev))
+        self.bias = tnn.Parameter(torch.zeros(dim, device=dev))
+        self._rt = None
+
+    def forward(self, x, add_slot=None):
+        """x: [N, H, W, dim] in the compute dtype."""
+        return _DepthwiseConvFn.apply(x, self.weight, self.bias, self, add_slot)
+
+
+class _PatchConvFn(Function):
+    """Biased kernel = stride convolution over NHWC on the implicit-GEMM kernel: the bias is the epilogue's ``shift``,
+    the data gradient goes through plan.dgrad_plan (stride 2 splits into residue classes), dW through wgrad_desc and
+    the bias gradient is the column sum of dy; both parameter gradients are ACCUMULATED, as Linear's are, on the side
+    stream when there is one."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, layer):
+        _need_contiguous('PatchConv2D', x=x)
+        rt = _need_rt(layer)
+        N, H, W = x.shape[0], x.shape[1], x.shape[2]
+        pl = layer._plan(N, H, W)
+        y = torch.empty(N, pl.fd.OP, pl.fd.OQ, layer.geom.cout, dtype=x.dtype, device=x.device)
+        ops.conv_igemm(pl.fd, x, rt.w_fwd, y, shift=bias.detach())
+        if any(ctx.needs_input_grad):
+            rt.arena.expect_grad(rt.indices)
+        ctx.save_for_backward(x)
+        ctx.layer, ctx.pl = layer, pl
+        ctx.side = streams.enabled(x)              # latched for the backward (see _ConvFn)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        layer, pl = ctx.layer, ctx.pl
+        rt, g = layer._rt, layer.geom
+        dy = dy.contiguous()
+        dx = None
+        if ctx.needs_input_grad[0]:
+            alloc = ops.zeros if pl.dgrad_zero else torch.empty
+            dx = alloc(x.shape[0], x.shape[1], x.shape[2], g.cin, dtype=dy.dtype, device=dy.device)
+            for d in pl.dds:
+                ops.conv_igemm(d, dy, rt.w_dgrad[id(d.pack)], dx)
+        rows = dy.view(-1, g.cout)
+        bias_grad = layer.bias.grad
+
+        def param_grads():
+            ops.conv_wgrad(pl.wd, x, rows, rt.dw)
+            ops.colsum_into(rows, bias_grad, accumulate=True)
+        if ctx.side:
+            streams.side_later(dy.device, param_grads, reads=(x, dy))
+        else:
+            param_grads()
+        rt.arena.grad_ready(rt.indices)
+        return dx, None, None, None
+
+
+class PatchConv2D(Layer):
+    """paddle.nn.Conv2D(cin, cout, kernel_size=k, stride=k) WITH bias over NHWC activations (ConvNeXt's 2x2/2 downsample
+    layers, convnext.py:140-141).  ``weight`` is logically [cout, cin, k, k] (the reference's layout) and physically
+    [cout][k][k][cin] in the arena, as Conv2D's.  Lives in an EncoderArena; ``Conv2D`` itself stays bias-free."""
+    krsc_weight = True
+    is_stem = False
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=None):
+        super().__init__()
+        stride = kernel_size if stride is None else stride
+        if stride != kernel_size:
+            raise NotImplementedError('PatchConv2D: stride %r != kernel_size %r (a patch convolution has kernel = stride)'
+                                      % (stride, kernel_size))
+        if in_channels % 8 or out_channels % 8:
+            raise NotImplementedError('PatchConv2D: channels (%d -> %d) must be multiples of 8'
+                                      % (in_channels, out_channels))
+        dev = config.get_device()
+        self.geom = P.ConvGeom(in_channels, out_channels, kernel_size, stride, 0)
+        self.weight = tnn.Parameter(torch.empty(out_channels, in_channels, kernel_size, kernel_size, device=dev))
+        self.bias = tnn.Parameter(torch.zeros(out_channels, device=dev))
+        self._rt = None
+        self._plans = {}
+
+    def _plan(self, N, H, W):
+        key = (N, H, W)
+        pl = self._plans.get(key)
+        if pl is None:
+            rt = _need_rt(self)
+            g = self.geom
+            if H % g.k or W % g.k:
+                raise NotImplementedError('PatchConv2D: input %d x %d is not a multiple of the patch %d' % (H, W, g.k))
+            dds, skipped = ([], False)
+            if rt.dgrad_packs is not None:
+                dds, skipped = P.dgrad_plan(g, N, H, W, packs=rt.dgrad_packs)
+            pl = SimpleNamespace(fd=P.fwd_desc(g, N, H, W), wd=P.wgrad_desc(g, N, H, W), dds=dds, dgrad_zero=skipped)
+            self._plans[key] = pl
+        return pl
+
+    def forward(self, x):
+        """x: [N, H, W, cin] in the compute dtype -> [N, H / k, W / k, cout]."""
+        return _PatchConvFn.apply(x, self.weight, self.bias, self)
+
+
+class _LayerScaleAddFn(Function):
+    """residual + keep_row[b] * ((gamma * branch) / keep_prob): the tail of a ConvNeXt block (convnext.py:100-102).
+    Backward: dbranch and dgamma (WRITTEN into gamma.grad) from one launch pair; the residual's gradient is dy itself:
+    returned to autograd, or put into res_slot for the depthwise convolution's data gradient to add."""
+
+    @staticmethod
+    def forward(ctx, branch, residual, gamma, keep_row, keep_prob, B, T, res_slot):
+        _need_contiguous('layer_scale_add', branch=branch, residual=residual)
+        ctx.save_for_backward(branch, keep_row)
+        ctx.gamma, ctx.args, ctx.res_slot = gamma, (keep_prob, B, T), res_slot
+        return ops.layer_scale_add_fwd(branch, residual, gamma.detach(), keep_row, keep_prob, B, T)
+
+    @staticmethod
+    def backward(ctx, dy):
+        branch, keep_row = ctx.saved_tensors
+        gamma, (keep_prob, B, T) = ctx.gamma, ctx.args
+        dy = dy.contiguous()
+        if gamma.grad is None:
+            gamma.grad = ops.zeros(*gamma.shape, dtype=gamma.dtype, device=gamma.device)
+        dbranch = ops.layer_scale_add_bwd_into(dy, branch, gamma.detach(), keep_row, keep_prob, B, T, gamma.grad)
+        param_grad_ready(gamma)
+        dres = dy
+        if ctx.res_slot is not None and ctx.res_slot.armed:
+            ctx.res_slot.put(dy)
+            dres = None
+        return dbranch, dres, None, None, None, None, None, None
+
+
+def layer_scale_add(branch, residual, gamma, keep_row, keep_prob, B, T, res_slot=None):
+    """branch, residual: rows [B*T, C]; gamma: fp32 [C] parameter; keep_row: fp32 [B] on the device (one row of the
+    model's keep table) or None (rate 0, evaluation)."""
+    param_expect_grad(gamma)
+    return _LayerScaleAddFn.apply(branch, residual, gamma, keep_row, keep_prob, B, T, res_slot)
+
+
 class DropoutState:
     """What the dropout sites of ONE model share (csrc/dropout.hip): the rate as (thr, factor), the Philox key, the
     step counter in device memory and the ordinal of the current training pass on the host.

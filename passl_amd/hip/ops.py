@@ -866,6 +866,66 @@ def drop_path_bwd(dy, keep_row, keep_prob, B, T):
     return dbranch
 
 
+# ------------------------------------------------------------------ ConvNeXt block (csrc/dwconv.hip)
+def dwconv7_wgrad_ws_floats(N, H, W, Cc):
+    """include/passl_hip.h: PASSL_DWCONV7_WGRAD_WS_FLOATS."""
+    return min(N * -(-H // 8) * -(-W // 16), 512) * 50 * Cc
+
+
+def layer_scale_bwd_ws_floats(M, Cc):
+    """include/passl_hip.h: PASSL_LAYER_SCALE_BWD_WS_FLOATS."""
+    rows_per = -(-M // 1024)
+    return -(-M // rows_per) * Cc
+
+
+def dwconv7_fwd(x, w, bias):
+    """Depthwise 7x7, padding 3: x NHWC [N, H, W, C]; w fp32 [C, 1, 7, 7] (the parameter as it lies), bias fp32 [C]."""
+    N, H, W, Cc = x.shape
+    y = torch.empty_like(x)
+    L.check(_lib().passl_hip_dwconv7_fwd(L.ptr(x), L.ptr(w), L.ptr(bias), L.ptr(y), N, H, W, Cc, L.dt(x), L.stream()),
+            'dwconv7_fwd')
+    return y
+
+
+def dwconv7_bwd_data(dy, w, add=None):
+    """dx of dwconv7_fwd (+ add, the gradient of the residual fork, inside the same rounding)."""
+    N, H, W, Cc = dy.shape
+    dx = torch.empty_like(dy)
+    L.check(_lib().passl_hip_dwconv7_bwd_data(L.ptr(dy), L.ptr(w), L.ptr(add), L.ptr(dx), N, H, W, Cc, L.dt(dy),
+                                              L.stream()), 'dwconv7_bwd_data')
+    return dx
+
+
+def dwconv7_bwd_weight_into(x, dy, dw, dbias):
+    """dw [C, 1, 7, 7] and dbias [C] (fp32, WRITTEN) of dwconv7_fwd."""
+    N, H, W, Cc = x.shape
+    ws = workspace.get(dwconv7_wgrad_ws_floats(N, H, W, Cc), x.device)
+    L.check(_lib().passl_hip_dwconv7_bwd_weight(L.ptr(x), L.ptr(dy), L.ptr(dw), L.ptr(dbias), L.ptr(ws), ws.numel(),
+                                                N, H, W, Cc, L.dt(x), L.stream()), 'dwconv7_bwd_weight')
+    return dw, dbias
+
+
+def layer_scale_add_fwd(branch, residual, gamma, keep_row, keep_prob, B, T):
+    """residual + keep_row[b] * ((gamma * branch) / keep_prob) over rows [B*T, C]; keep_row None: rate 0 / evaluation."""
+    Cc = branch.shape[-1]
+    out = torch.empty_like(branch)
+    L.check(_lib().passl_hip_layer_scale_add_fwd(L.ptr(branch), L.ptr(residual), L.ptr(gamma), L.ptr(keep_row),
+                                                 keep_prob, L.ptr(out), B, T, Cc, L.dt(branch), L.stream()),
+            'layer_scale_add_fwd')
+    return out
+
+
+def layer_scale_add_bwd_into(dy, branch, gamma, keep_row, keep_prob, B, T, dgamma):
+    """-> dbranch; dgamma [C] (fp32) is WRITTEN."""
+    Cc = dy.shape[-1]
+    dbranch = torch.empty_like(dy)
+    ws = workspace.get(layer_scale_bwd_ws_floats(B * T, Cc), dy.device)
+    L.check(_lib().passl_hip_layer_scale_add_bwd(L.ptr(dy), L.ptr(branch), L.ptr(gamma), L.ptr(keep_row), keep_prob,
+                                                 L.ptr(dbranch), L.ptr(dgamma), L.ptr(ws), ws.numel(), B, T, Cc,
+                                                 L.dt(dy), L.stream()), 'layer_scale_add_bwd')
+    return dbranch
+
+
 # ------------------------------------------------------------------ element-wise dropout (csrc/dropout.hip)
 def dropout_params(p):
     """-> (thr, factor) of rate ``p``: thr = floor(p * 65536 + 0.5) in double, factor = float32(1 / (1 - float32(p)))
