@@ -790,6 +790,43 @@ int passl_hip_layer_scale_add_bwd(const void* dy, const void* branch, const floa
                                   float keep_prob, void* dbranch, float* dgamma, float* ws, int64_t ws_floats, int B,
                                   int T, int C, int dtype, passl_stream_t stream);
 
+/* ---------------------------------------------------------------- Swin Transformer (csrc/window_attention.hip)
+ * Reference: WindowAttention.forward, passl/models/swin_transformer.py:112-200, with the roll, window_partition,
+ * attn_mask, window_reverse and roll of SwinTransformerBlock.forward :291-340 as address arithmetic.
+ * qkv [B, Hp*Wp, 3, nH, DH] in `dtype`: the qkv projection of the UNSHIFTED, UNPARTITIONED tokens; out, dout
+ * [B, Hp*Wp, nH, DH] in the same token order; table fp32 [(2 ws - 1)^2, nH], the relative_position_bias_table as it
+ * lies; lse fp32 [B * nW, nH, T], nW = (Hp / ws)(Wp / ws), T = ws^2.  Token i = (iy, ix) of window (wy, wx) is row
+ * ((wy ws + iy + shift) mod Hp) Wp + ((wx ws + ix + shift) mod Wp) of its image, and
+ * score[i, j] = (q_i . k_j) scale + table[(iy - jy + ws - 1)(2 ws - 1) + (ix - jx + ws - 1), h] + m[i, j] in fp32;
+ * for shift > 0, m = -100 where label(i) != label(j), label = 3 r(wy ws + iy, Hp) + r(wx ws + ix, Wp),
+ * r(y, n) = 0 if y < n - ws, 1 if y < n - shift, else 2.
+ * Accepted: 1 <= ws <= 14, DH in {32, 64} (PASSL_EUNSUPPORTED otherwise); Hp, Wp multiples of ws, 0 <= shift < ws,
+ * shift > 0 only with min(Hp, Wp) > ws, bf16 tensors 16-byte aligned (PASSL_EINVAL otherwise). */
+int passl_hip_window_attention_fwd(const void* qkv, const float* table, void* out, float* lse, int B, int Hp, int Wp,
+                                   int ws, int shift, int nH, int DH, float scale, int dtype, passl_stream_t stream);
+/* dqkv [B, Hp*Wp, 3, nH, DH] (fully written) and dtable fp32 [(2 ws - 1)^2, nH] (WRITTEN) = the sum of
+ * dS = P (dP - delta) over every image, window and pair of a bin, taken from the fp32 dS.  No atomics: `slabs` =
+ * min(ceil(windows / 2), 2048 / nH) workgroups per head each walk a fixed set of windows and write one [T, T] partial to ws_buf, which two small launches
+ * add in slab order and fold into the bins in a fixed order; two runs give the same bits.
+ * ws_floats >= PASSL_WINDOW_ATTENTION_WS_FLOATS(B * nW, nH, ws). */
+#define PASSL_WINDOW_ATTENTION_WORKGROUPS 2048 /* slabs * nH aims at this many: about eight per CU */
+#define PASSL_WINDOW_ATTENTION_SLABS(windows, nH)                                                         \
+  ((((windows) + 1) / 2) < (PASSL_WINDOW_ATTENTION_WORKGROUPS / (nH) > 0 ? PASSL_WINDOW_ATTENTION_WORKGROUPS / (nH) : 1) \
+       ? (((windows) + 1) / 2)                                                                            \
+       : (PASSL_WINDOW_ATTENTION_WORKGROUPS / (nH) > 0 ? PASSL_WINDOW_ATTENTION_WORKGROUPS / (nH) : 1))
+#define PASSL_WINDOW_ATTENTION_WS_FLOATS(windows, nH, ws) \
+  ((int64_t)PASSL_WINDOW_ATTENTION_SLABS(windows, nH) * (nH) * (ws) * (ws) * (ws) * (ws))
+int passl_hip_window_attention_bwd(const void* qkv, const float* table, const void* out, const void* dout,
+                                   const float* lse, void* dqkv, float* dtable, float* ws_buf, int64_t ws_floats, int B,
+                                   int Hp, int Wp, int ws, int shift, int nH, int DH, float scale, int dtype,
+                                   passl_stream_t stream);
+/* PatchMerging's gather (swin_transformer.py:343-384): x [B, H, W, C] -> y [B, H/2, W/2, 4C],
+ * y[b, oy, ox, k C + c] = x[b, 2 oy + (k & 1), 2 ox + (k >> 1), c] (x0, x1, x2, x3 of the reference), one streaming
+ * launch of 16-byte accesses.  H, W even, C % 8 == 0, 16-byte aligned tensors (PASSL_EINVAL otherwise).  _bwd: the
+ * inverse copy, dx [B, H, W, C] fully written from dy [B, H/2, W/2, 4C]. */
+int passl_hip_patch_merge(const void* x, void* y, int B, int H, int W, int C, int dtype, passl_stream_t stream);
+int passl_hip_patch_merge_bwd(const void* dy, void* dx, int B, int H, int W, int C, int dtype, passl_stream_t stream);
+
 /* ---------------------------------------------------------------- mixup / cutmix and soft-target cross-entropy
  * Reference: class Mixup, passl_v110/datasets/preprocess/mixup.py:108-276 (the reference mixes on the host, in numpy or
  * through the framework's CPU tensors); SoftTargetCrossEntropy, tasks/ssl/mae/util/loss.py:44-47. */

@@ -315,11 +315,23 @@ class Engine(object):
             if klass not in (OPTIMIZERS.get('AdamW'), OPTIMIZERS.get('Adan')):
                 raise NotImplementedError('Optimizer.grad_clip is built for Adan and AdamW only, not for %s' % name)
             opt_cfg['grad_clip'] = build_grad_clip(grad_clip)
-        for k in ('no_weight_decay_name', 'layer_decay'):
-            if opt_cfg.get(k, None) not in (None, [], ''):
-                raise NotImplementedError('Optimizer.%s is not built on the HIP path (pre-training recipes of '
-                                          'tasks/ssl do not use it)' % k)
-            opt_cfg.pop(k, None)
+        # no_weight_decay_name (passl/optimizer/utils/group_params.py:171-180): a trainable parameter whose name contains
+        # any listed string gets decay 0.  AdamW only: its grouped launch takes the two groups (solver/optimizer.py)
+        no_decay = opt_cfg.pop('no_weight_decay_name', None)
+        if no_decay not in (None, [], ''):
+            if klass is not OPTIMIZERS.get('AdamW'):
+                raise NotImplementedError('Optimizer.no_weight_decay_name is built for AdamW only, not for %s' % name)
+            if groups_cfg:
+                raise NotImplementedError('Optimizer.no_weight_decay_name together with Optimizer.param_groups is not '
+                                          'built (no recipe sets both)')
+            if isinstance(no_decay, str):
+                no_decay = [no_decay]
+            self.optimizer = klass(lr, **opt_cfg, **{key: self._decay_groups(list(no_decay))})
+            return
+        if opt_cfg.get('layer_decay', None) not in (None, [], ''):
+            raise NotImplementedError('Optimizer.layer_decay is not built on the HIP path (pre-training recipes of '
+                                      'tasks/ssl do not use it)')
+        opt_cfg.pop('layer_decay', None)
         if groups_cfg:
             self.optimizer = OptimizerGroup(klass, key, self._group_params(groups_cfg), lr, opt_cfg,
                                             lambda c: self._build_scheduler(dict(c, decay_unit=self.lr_decay_unit), g))
@@ -340,6 +352,20 @@ class Engine(object):
         if 'step_each_epoch' in accepted:
             sched_cfg.update({'epochs': g['epochs'], 'step_each_epoch': len(self.train_dataloader), 'decay_unit': unit})
         return build_from_config(sched_cfg, LRSCHEDULERS)
+
+    def no_weight_decay_names(self, no_decay):
+        """Names of the trainable parameters that contain any string of ``no_decay``, in model order."""
+        return [n for n, p in self.model.named_parameters() if p.requires_grad and any(nd in n for nd in no_decay)]
+
+    def _decay_groups(self, no_decay):
+        """-> the decay and the no-decay group of the optimizer's ``parameters`` (an empty group is left out)."""
+        skip = set(self.no_weight_decay_names(no_decay))
+        named = [(n, p) for n, p in self.model.named_parameters() if p.requires_grad]
+        groups = [{'params': [p for n, p in named if n not in skip]},
+                  {'params': [p for n, p in named if n in skip], 'weight_decay': 0.0}]
+        self.logger.info('weight_decay-params length: %d, no_weight_decay-params length: %d',
+                         len(groups[0]['params']), len(groups[1]['params']))
+        return [g for g in groups if g['params']]
 
     def _group_params(self, groups_cfg):
         """group_params (passl/optimizer/__init__.py:68-113) -> [(group config, [parameters])] in config order,

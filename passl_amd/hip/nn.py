@@ -1318,6 +1318,61 @@ def attention(qkv, B, T, H, DH, scale, causal=False):
     return _AttentionFn.apply(qkv, B, T, H, DH, float(scale), bool(causal))
 
 
+class _WindowAttentionFn(Function):
+    """Shifted-window attention with the relative-position bias (csrc/window_attention.hip) on the qkv projection of the
+    unshifted, unpartitioned tokens.  Backward: dqkv, and dtable WRITTEN into table.grad."""
+
+    @staticmethod
+    def forward(ctx, qkv, table, B, Hp, Wp, ws, shift, nH, DH, scale):
+        _need_contiguous('window_attention', qkv=qkv)
+        out, lse = ops.window_attention_fwd(qkv, table.detach(), B, Hp, Wp, ws, shift, nH, DH, scale)
+        ctx.save_for_backward(qkv, out, lse)
+        ctx.table, ctx.dims = table, (B, Hp, Wp, ws, shift, nH, DH, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse = ctx.saved_tensors
+        table = ctx.table
+        from_arena = getattr(table, '_passl_arena', None) is not None
+        dtable = table.grad if from_arena else None
+        if dtable is None:
+            dtable = ops.zeros(*table.shape, dtype=table.dtype, device=table.device)
+            if from_arena:
+                table.grad = dtable
+        dqkv = ops.window_attention_bwd_into(qkv, table.detach(), out, dout.contiguous(), lse, dtable, *ctx.dims)
+        if from_arena:
+            param_grad_ready(table)
+            return (dqkv,) + (None,) * 9
+        return (dqkv, dtable) + (None,) * 8
+
+
+def window_attention(qkv, table, B, Hp, Wp, ws, shift, nH, DH, scale):
+    """qkv: rows [B*Hp*Wp, 3*nH*DH]; table: the fp32 [(2 ws - 1)^2, nH] relative_position_bias_table.  A table that is
+    a parameter of an arena has its gradient written in place (as layer_scale_add's gamma); any other tensor gets it
+    from autograd."""
+    param_expect_grad(table)
+    return _WindowAttentionFn.apply(qkv, table, B, Hp, Wp, ws, shift, nH, DH, float(scale))
+
+
+class _PatchMergeFn(Function):
+    """PatchMerging's gather of four neighbours [B*H*W, C] -> [B*(H/2)*(W/2), 4C]; the backward is the inverse copy."""
+
+    @staticmethod
+    def forward(ctx, x, B, H, W):
+        _need_contiguous('patch_merge', x=x)
+        ctx.dims = (B, H, W)
+        return ops.patch_merge(x, B, H, W)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ops.patch_merge_bwd(dy.contiguous(), *ctx.dims), None, None, None
+
+
+def patch_merge(x, B, H, W):
+    return _PatchMergeFn.apply(x, B, H, W)
+
+
 class QuickGELU(Layer):
     """x * sigmoid(1.702 x) (passl_v110/modeling/backbones/base_transformer.py:25-28)."""
 

@@ -783,6 +783,53 @@ def attention_bwd(qkv, out, dout, lse, B, T, H, DH, scale, causal=False):
     return dqkv
 
 
+# ------------------------------------------------------------------ Swin Transformer (csrc/window_attention.hip)
+WINDOW_ATTENTION_MAX_WINDOW = 14
+WINDOW_ATTENTION_WORKGROUPS = 2048   # include/passl_hip.h: PASSL_WINDOW_ATTENTION_WORKGROUPS
+
+
+def window_attention_ws_floats(windows, nH, ws):
+    """include/passl_hip.h: PASSL_WINDOW_ATTENTION_WS_FLOATS."""
+    return min((windows + 1) // 2, max(WINDOW_ATTENTION_WORKGROUPS // nH, 1)) * nH * ws ** 4
+
+
+def window_attention_fwd(qkv, table, B, Hp, Wp, ws, shift, nH, DH, scale):
+    """qkv [B*Hp*Wp, 3*nH*DH] of the unshifted, unpartitioned tokens, table fp32 [(2 ws - 1)^2, nH] ->
+    out [B*Hp*Wp, nH*DH] in the same token order, lse fp32 [B*nW, nH, ws^2]."""
+    out = torch.empty(B * Hp * Wp, nH * DH, dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty(B * (Hp // max(ws, 1)) * (Wp // max(ws, 1)), nH, ws * ws, dtype=torch.float32, device=qkv.device)
+    L.check(_lib().passl_hip_window_attention_fwd(L.ptr(qkv), L.ptr(table), L.ptr(out), L.ptr(lse), B, Hp, Wp, ws,
+                                                  shift, nH, DH, scale, L.dt(qkv), L.stream()), 'window_attention_fwd')
+    return out, lse
+
+
+def window_attention_bwd_into(qkv, table, out, dout, lse, dtable, B, Hp, Wp, ws, shift, nH, DH, scale):
+    """-> dqkv; dtable fp32 [(2 ws - 1)^2, nH] is WRITTEN."""
+    dqkv = torch.empty_like(qkv)
+    buf = workspace.get(window_attention_ws_floats(B * (Hp // ws) * (Wp // ws), nH, ws), qkv.device)
+    L.check(_lib().passl_hip_window_attention_bwd(L.ptr(qkv), L.ptr(table), L.ptr(out), L.ptr(dout), L.ptr(lse),
+                                                  L.ptr(dqkv), L.ptr(dtable), L.ptr(buf), buf.numel(), B, Hp, Wp, ws,
+                                                  shift, nH, DH, scale, L.dt(qkv), L.stream()), 'window_attention_bwd')
+    return dqkv
+
+
+def patch_merge(x, B, H, W):
+    """Rows [B*H*W, C] -> [B*(H/2)*(W/2), 4C]: the x0, x1, x2, x3 gather of PatchMerging (swin_transformer.py:343-384)."""
+    Cc = x.shape[-1]
+    y = torch.empty(B * (H // 2) * (W // 2), 4 * Cc, dtype=x.dtype, device=x.device)
+    L.check(_lib().passl_hip_patch_merge(L.ptr(x), L.ptr(y), B, H, W, Cc, L.dt(x), L.stream()), 'patch_merge')
+    return y
+
+
+def patch_merge_bwd(dy, B, H, W):
+    """The inverse copy: dy [B*(H/2)*(W/2), 4C] -> dx [B*H*W, C], fully written."""
+    Cc = dy.shape[-1] // 4
+    dx = torch.empty(B * H * W, Cc, dtype=dy.dtype, device=dy.device)
+    L.check(_lib().passl_hip_patch_merge_bwd(L.ptr(dy), L.ptr(dx), B, H, W, Cc, L.dt(dy), L.stream()),
+            'patch_merge_bwd')
+    return dx
+
+
 def mae_mask(noise, len_keep):
     B, Ln = noise.shape
     dev = noise.device

@@ -24,7 +24,8 @@ from ..hip import config, nn, ops, plan as P
 
 
 def to_2tuple(x):
-    return tuple([x] * 2)
+    """(x, x); a pair passes through (a non-square image size, as swin_transformer.py's own to_2tuple allows)."""
+    return tuple(x) if isinstance(x, (tuple, list)) else (x, x)
 
 
 def process_rank():
