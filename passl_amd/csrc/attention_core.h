@@ -29,7 +29,8 @@
 //   kAccumByLane         accum takes the whole lane, not (l15, l4)
 //   kSelectProb          dQ sweep: form prob for every lane and select (the tile stays one basic block and the
 //                        MFMA chains of its two scores interleave) rather than branch around it
-//   stage<NTH>           rows [0, Tn) of a strided matrix -> LDS [Tpad][P]; rows >= Tn are zero
+//   stage<NTH>           rows rows.row(0 .. Tn - 1) of a strided matrix -> LDS [Tpad][P]; rows >= Tn are zero.  `rows` maps
+//                        a token to its row: SameRows here, the window's row numbers in window_attention.hip
 //   load_own             fragment of an own row from global memory, zero when invalid
 //   dot                  acc[r] = own[row l15] . swept[row tile*16 + 4*l4 + r]
 //   accum                o[own = 4*l4' + r'][d = jd*16 + l15] += sum over the 16 * kStep rows of tiles [t0, t0 + kStep)
@@ -73,6 +74,11 @@ constexpr int lds_bytes(int Tpad, bool stats) {
 template <class Ops>
 constexpr int max_lds() { return lds_bytes<Ops>(Ops::kMaxRows, true); }
 
+// the row map of tokens that lie where they are counted
+struct SameRows {
+  __device__ __forceinline__ int row(int t) const { return t; }
+};
+
 // Ops::accum, handed the kernel's `lane` or its `l15`, `l4`, whichever the policy's address arithmetic is written in:
 // naming the other one as well, even unused, reorders the instructions of every kernel of that policy
 #define ATTN_ACCUM(c, lds, t0, o)                                     \
@@ -95,8 +101,8 @@ __global__ void __launch_bounds__(NW * 64, Ops::fwd_waves_per_eu(NW)) attn_fwd_k
   L* Ks = reinterpret_cast<L*>(smem);
   L* Vs = Ks + Tpad * P;
   const int64_t rs = (int64_t)3 * H * DH;
-  Ops::template stage<NW * 64>(qkv + qkv_off<DH>(b, 0, 1, h, Tn, H), rs, Tn, Tpad, Ks);
-  Ops::template stage<NW * 64>(qkv + qkv_off<DH>(b, 0, 2, h, Tn, H), rs, Tn, Tpad, Vs);
+  Ops::template stage<NW * 64>(qkv + qkv_off<DH>(b, 0, 1, h, Tn, H), rs, SameRows{}, Tn, Tpad, Ks);
+  Ops::template stage<NW * 64>(qkv + qkv_off<DH>(b, 0, 2, h, Tn, H), rs, SameRows{}, Tn, Tpad, Vs);
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int l15 = lane & 15, l4 = lane >> 4;
@@ -178,8 +184,8 @@ __global__ void __launch_bounds__(NW * 64) attn_bwd_q_kernel(
   L* Ks = reinterpret_cast<L*>(smem);
   L* Vs = Ks + Tpad * P;
   const int64_t rs = (int64_t)3 * H * DH;
-  Ops::template stage<NW * 64>(qkv + qkv_off<DH>(b, 0, 1, h, Tn, H), rs, Tn, Tpad, Ks);
-  Ops::template stage<NW * 64>(qkv + qkv_off<DH>(b, 0, 2, h, Tn, H), rs, Tn, Tpad, Vs);
+  Ops::template stage<NW * 64>(qkv + qkv_off<DH>(b, 0, 1, h, Tn, H), rs, SameRows{}, Tn, Tpad, Ks);
+  Ops::template stage<NW * 64>(qkv + qkv_off<DH>(b, 0, 2, h, Tn, H), rs, SameRows{}, Tn, Tpad, Vs);
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int l15 = lane & 15, l4 = lane >> 4;
@@ -255,8 +261,8 @@ __global__ void __launch_bounds__(NW * 64) attn_bwd_kv_kernel(
   L* Ds = Qs + Tpad * P;                                         // dO
   float* Ls = reinterpret_cast<float*>(Qs + 2 * Tpad * P);       // lse[Tpad]
   float* Dl = Ls + Tpad;                                         // delta[Tpad]
-  Ops::template stage<NW * 64>(qkv + qkv_off<DH>(b, 0, 0, h, Tn, H), (int64_t)3 * H * DH, Tn, Tpad, Qs);
-  Ops::template stage<NW * 64>(dout + (((int64_t)b * Tn) * H + h) * DH, (int64_t)H * DH, Tn, Tpad, Ds);
+  Ops::template stage<NW * 64>(qkv + qkv_off<DH>(b, 0, 0, h, Tn, H), (int64_t)3 * H * DH, SameRows{}, Tn, Tpad, Qs);
+  Ops::template stage<NW * 64>(dout + (((int64_t)b * Tn) * H + h) * DH, (int64_t)H * DH, SameRows{}, Tn, Tpad, Ds);
   __syncthreads();
   for (int t = threadIdx.x; t < Tpad; t += NW * 64) {
     float d = 0.f, l = 0.f;
@@ -323,19 +329,25 @@ __global__ void __launch_bounds__(NW * 64) attn_bwd_kv_kernel(
 }
 
 // ------------------------------------------------------------------ launches
+// one sweep: `groups` workgroups of NW waves with `lds` bytes of dynamic LDS; the kernel's cap is raised to `cap` once
+template <auto Kernel, int NW, class... A>
+int launch_sweep(int groups, int lds, int cap, hipStream_t st, A... a) {
+  static bool capped = false;
+  if (!capped) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, cap);
+    capped = true;
+  }
+  hipLaunchKernelGGL(Kernel, dim3(groups), dim3(NW * 64), lds, st, a...);
+  return hipGetLastError() == hipSuccess ? PASSL_OK : PASSL_ELAUNCH;
+}
+
 template <class Ops, int NW>
 int launch_fwd(const void* qkv, void* out, float* lse, int B, int Tn, int H, float scale, int causal,
                hipStream_t st) {
   using T = typename Ops::elem_t;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel<Ops, NW>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, max_lds<Ops>());
-    attr = true;
-  }
-  hipLaunchKernelGGL((attn_fwd_kernel<Ops, NW>), dim3(B * H), dim3(NW * 64), lds_bytes<Ops>(pad_rows<Ops>(Tn), false),
-                     st, reinterpret_cast<const T*>(qkv), reinterpret_cast<T*>(out), lse, Tn, H, scale, causal);
-  return hipGetLastError() == hipSuccess ? PASSL_OK : PASSL_ELAUNCH;
+  return launch_sweep<&attn_fwd_kernel<Ops, NW>, NW>(B * H, lds_bytes<Ops>(pad_rows<Ops>(Tn), false), max_lds<Ops>(), st,
+                                                    reinterpret_cast<const T*>(qkv), reinterpret_cast<T*>(out), lse, Tn,
+                                                    H, scale, causal);
 }
 
 template <class Ops, int NW>
@@ -343,22 +355,12 @@ int launch_bwd(const void* qkv, const void* out, const void* dout, const float* 
                int Tn, int H, float scale, int causal, hipStream_t st) {
   using T = typename Ops::elem_t;
   const int Tpad = pad_rows<Ops>(Tn);
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_q_kernel<Ops, NW>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, max_lds<Ops>());
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kv_kernel<Ops, NW>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, max_lds<Ops>());
-    attr = true;
-  }
-  hipLaunchKernelGGL((attn_bwd_q_kernel<Ops, NW>), dim3(B * H), dim3(NW * 64), lds_bytes<Ops>(Tpad, false), st,
-                     reinterpret_cast<const T*>(qkv), reinterpret_cast<const T*>(out),
-                     reinterpret_cast<const T*>(dout), lse, reinterpret_cast<T*>(dqkv), Tn, H, scale, causal);
-  if (hipGetLastError() != hipSuccess) return PASSL_ELAUNCH;
-  hipLaunchKernelGGL((attn_bwd_kv_kernel<Ops, NW>), dim3(B * H), dim3(NW * 64), lds_bytes<Ops>(Tpad, true), st,
-                     reinterpret_cast<const T*>(qkv), reinterpret_cast<const T*>(out),
-                     reinterpret_cast<const T*>(dout), lse, reinterpret_cast<T*>(dqkv), Tn, H, scale, causal);
-  return hipGetLastError() == hipSuccess ? PASSL_OK : PASSL_ELAUNCH;
+  const T *q = reinterpret_cast<const T*>(qkv), *o = reinterpret_cast<const T*>(out), *d = reinterpret_cast<const T*>(dout);
+  const int rc = launch_sweep<&attn_bwd_q_kernel<Ops, NW>, NW>(B * H, lds_bytes<Ops>(Tpad, false), max_lds<Ops>(), st, q, o,
+                                                                d, lse, reinterpret_cast<T*>(dqkv), Tn, H, scale, causal);
+  if (rc != PASSL_OK) return rc;
+  return launch_sweep<&attn_bwd_kv_kernel<Ops, NW>, NW>(B * H, lds_bytes<Ops>(Tpad, true), max_lds<Ops>(), st, q, o, d, lse,
+                                                         reinterpret_cast<T*>(dqkv), Tn, H, scale, causal);
 }
 
 // f(std::integral_constant<int, DH>) for the two head dimensions the kernels are built for

@@ -1,5 +1,6 @@
 // Operand policy of the bf16-MFMA attention kernels (attention_core.h lists what a policy supplies); shared by
-// attention_bf16.hip, which describes the operand layout, and window_attention.hip.
+// attention_bf16.hip, which describes the operand layout, and window_attention.hip, whose staging differs only in the
+// row map it hands to stage.
 #pragma once
 #include "attention_core.h"
 
@@ -21,14 +22,14 @@ struct Bf16Ops {
   static constexpr bool kAccumByLane = true;
   static constexpr bool kSelectProb = false;     // the select costs the 8-wave d = 64 dQ sweep 6 VGPRs: 5 waves, not 6
 
-  template <int NTH>
-  __device__ static __forceinline__ void stage(const bf16_t* __restrict__ base, int64_t rs, int Tn, int Tpad,
-                                               bf16_t* lds) {
+  template <int NTH, class Rows>
+  __device__ static __forceinline__ void stage(const bf16_t* __restrict__ base, int64_t rs, const Rows& rows, int Tn,
+                                               int Tpad, bf16_t* lds) {
     constexpr int CH = DH / 8;
     for (int i = threadIdx.x; i < Tpad * CH; i += NTH) {
       const int r = i / CH, c = (i % CH) * 8;
       uint4 v = make_uint4(0u, 0u, 0u, 0u);
-      if (r < Tn) v = *reinterpret_cast<const uint4*>(base + (int64_t)r * rs + c);
+      if (r < Tn) v = *reinterpret_cast<const uint4*>(base + (int64_t)rows.row(r) * rs + c);
       *reinterpret_cast<uint4*>(lds + r * P + c) = v;
     }
   }

@@ -1,5 +1,5 @@
 // Operand policy of the exact-fp32-MFMA attention kernels (attention_core.h lists what a policy supplies); shared by
-// attention.hip and window_attention.hip.
+// attention.hip and window_attention.hip, whose staging differs only in the row map it hands to stage.
 //
 // LDS holds fp32 rows [T_pad][d + 4] (bf16 inputs are converted when staged); every product is
 // v_mfma_f32_16x16x4_f32, one tile per accumulate step.
@@ -24,14 +24,14 @@ struct F32Ops {
   static constexpr bool kAccumByLane = false;
   static constexpr bool kSelectProb = true;      // one wave per SIMD at T = 197: nothing else hides an MFMA chain
 
-  template <int NTH>
-  __device__ static __forceinline__ void stage(const T* __restrict__ base, int64_t rs, int Tn, int Tpad,
-                                               float* lds) {
+  template <int NTH, class Rows>
+  __device__ static __forceinline__ void stage(const T* __restrict__ base, int64_t rs, const Rows& rows, int Tn,
+                                               int Tpad, float* lds) {
     for (int i = threadIdx.x; i < Tpad * (DH / 4); i += NTH) {
       const int r = i / (DH / 4), c = (i % (DH / 4)) * 4;
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
       if (r < Tn) {
-        const T* p = base + (int64_t)r * rs + c;
+        const T* p = base + (int64_t)rows.row(r) * rs + c;
         v = make_float4(ElemTraits<T>::ld(p), ElemTraits<T>::ld(p + 1), ElemTraits<T>::ld(p + 2),
                         ElemTraits<T>::ld(p + 3));
       }

@@ -3,8 +3,10 @@
 // Reference: WindowAttention.forward, passl/models/swin_transformer.py:112-200, and the roll / window_partition /
 // attn_mask / window_reverse / roll of SwinTransformerBlock.forward :291-340; PatchMerging.forward :343-384.
 //
-// Window attention.  The kernels are the three of attention_core.h (same operand policies, same MFMA tiling, same
-// softmax in registers) with two changes:
+// Window attention.  The kernels are the three of attention_core.h (same operand policies and, through a row map, the
+// same Ops::stage; same MFMA tiling, same softmax in registers; launched by attn::launch_sweep) with two changes.  They
+// are a second copy of the sweeps and not a policy of the first: DESIGN 33 has what was tried and what it did to the
+// dense kernels' code.
 //   * Tokens are addressed, not moved.  qkv [B, Hp*Wp, 3, nH, DH] is the projection of the unshifted, unpartitioned
 //     map.  Token i = (iy, ix) of window (wy, wx) is row ((wy ws + iy + shift) mod Hp) Wp + ((wx ws + ix + shift) mod Wp)
 //     of its image: roll(-shift), window_partition, window_reverse and roll(+shift) never run.  A window's row numbers
@@ -93,33 +95,11 @@ __device__ __forceinline__ void window_tokens(const Geo& g, int w, int Tn, int T
   }
 }
 
-// Ops::stage through the row numbers: rows[r] * rs is the offset of row r, rows >= Tn are zero
-template <class Ops, int NTH>
-__device__ __forceinline__ void stage_rows(const typename Ops::elem_t* __restrict__ base, int64_t rs, const int* rows,
-                                           int Tn, int Tpad, typename Ops::lds_t* lds) {
-  using T = typename Ops::elem_t;
-  constexpr int DH = Ops::DH, P = Ops::P;
-  if constexpr (std::is_same<typename Ops::lds_t, float>::value) {
-    for (int i = threadIdx.x; i < Tpad * (DH / 4); i += NTH) {
-      const int r = i / (DH / 4), c = (i % (DH / 4)) * 4;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (r < Tn) {
-        const T* p = base + (int64_t)rows[r] * rs + c;
-        v = make_float4(ElemTraits<T>::ld(p), ElemTraits<T>::ld(p + 1), ElemTraits<T>::ld(p + 2),
-                        ElemTraits<T>::ld(p + 3));
-      }
-      *reinterpret_cast<float4*>(lds + r * P + c) = v;
-    }
-  } else {
-    constexpr int CH = DH / 8;
-    for (int i = threadIdx.x; i < Tpad * CH; i += NTH) {
-      const int r = i / CH, c = (i % CH) * 8;
-      uint4 v = make_uint4(0u, 0u, 0u, 0u);
-      if (r < Tn) v = *reinterpret_cast<const uint4*>(base + (int64_t)rows[r] * rs + c);
-      *reinterpret_cast<uint4*>(lds + r * P + c) = v;
-    }
-  }
-}
+// Ops::stage's row map of a window: token t lies in row rows[t] of its image
+struct Rows {
+  const int* rows;
+  __device__ __forceinline__ int row(int t) const { return rows[t]; }
+};
 
 template <class Ops, class Coef>
 __device__ __forceinline__ void accum(const Coef& c, const typename Ops::lds_t* lds, int t0, int lane,
@@ -152,8 +132,8 @@ __global__ void __launch_bounds__(NW * 64) wattn_fwd_kernel(
   const int64_t rs = (int64_t)3 * g.nH * DH;
   const int64_t Limg = (int64_t)g.Hp * g.Wp;
   const T* img = qkv + (int64_t)b * Limg * rs + h * DH;
-  stage_rows<Ops, NW * 64>(img + g.nH * DH, rs, rows, Tn, Tpad, Ks);
-  stage_rows<Ops, NW * 64>(img + 2 * g.nH * DH, rs, rows, Tn, Tpad, Vs);
+  Ops::template stage<NW * 64>(img + g.nH * DH, rs, Rows{rows}, Tn, Tpad, Ks);
+  Ops::template stage<NW * 64>(img + 2 * g.nH * DH, rs, Rows{rows}, Tn, Tpad, Vs);
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int l15 = lane & 15, l4 = lane >> 4;
@@ -260,8 +240,8 @@ __global__ void __launch_bounds__(NW * 64) wattn_bwd_q_kernel(
     window_tokens<NW * 64>(g, w, Tn, Tpad, rows, tok);
     __syncthreads();
     const T* img = qkv + (int64_t)b * Limg * rs + h * DH;
-    stage_rows<Ops, NW * 64>(img + g.nH * DH, rs, rows, Tn, Tpad, Ks);
-    stage_rows<Ops, NW * 64>(img + 2 * g.nH * DH, rs, rows, Tn, Tpad, Vs);
+    Ops::template stage<NW * 64>(img + g.nH * DH, rs, Rows{rows}, Tn, Tpad, Ks);
+    Ops::template stage<NW * 64>(img + 2 * g.nH * DH, rs, Rows{rows}, Tn, Tpad, Vs);
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < RB; ++k) {
@@ -362,8 +342,8 @@ __global__ void __launch_bounds__(NW * 64) wattn_bwd_kv_kernel(
   const int64_t Limg = (int64_t)g.Hp * g.Wp;
   const T* img = qkv + (int64_t)b * Limg * rs + h * DH;
   const T* oimg = out + (int64_t)b * Limg * os + h * DH;
-  stage_rows<Ops, NW * 64>(img, rs, rows, Tn, Tpad, Qs);
-  stage_rows<Ops, NW * 64>(dout + (int64_t)b * Limg * os + h * DH, os, rows, Tn, Tpad, Ds);
+  Ops::template stage<NW * 64>(img, rs, Rows{rows}, Tn, Tpad, Qs);
+  Ops::template stage<NW * 64>(dout + (int64_t)b * Limg * os + h * DH, os, Rows{rows}, Tn, Tpad, Ds);
   __syncthreads();
   for (int t = threadIdx.x; t < Tpad; t += NW * 64) {
     float d = 0.f, l = 0.f;
@@ -467,44 +447,26 @@ template <class Ops, int NW, int NT>
 int launch_fwd(const void* qkv, const float* table, void* out, float* lse, int B, const Geo& g, float scale,
                hipStream_t st) {
   using T = typename Ops::elem_t;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wattn_fwd_kernel<Ops, NW, NT>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds_total<Ops>(padded_tiles<Ops>(NT) * 16, true, kMaxWindow));
-    attr = true;
-  }
-  const int Tpad = pad_rows<Ops>(g.ws * g.ws);
-  hipLaunchKernelGGL((wattn_fwd_kernel<Ops, NW, NT>), dim3(B * g.nW * g.nH), dim3(NW * 64),
-                     lds_total<Ops>(Tpad, false, g.ws), st, reinterpret_cast<const T*>(qkv), table,
-                     reinterpret_cast<T*>(out), lse, g, scale);
-  return hipGetLastError() == hipSuccess ? PASSL_OK : PASSL_ELAUNCH;
+  return attn::launch_sweep<&wattn_fwd_kernel<Ops, NW, NT>, NW>(
+      B * g.nW * g.nH, lds_total<Ops>(pad_rows<Ops>(g.ws * g.ws), false, g.ws),
+      lds_total<Ops>(padded_tiles<Ops>(NT) * 16, true, kMaxWindow), st, reinterpret_cast<const T*>(qkv), table,
+      reinterpret_cast<T*>(out), lse, g, scale);
 }
 
 template <class Ops, int NW, int NT>
 int launch_bwd(const void* qkv, const float* table, const void* out, const void* dout, const float* lse, void* dqkv,
                float* dtable, float* ws, int B, const Geo& g, float scale, hipStream_t st) {
   using T = typename Ops::elem_t;
-  static bool attr = false;
-  if (!attr) {
-    const int cap = lds_total<Ops>(padded_tiles<Ops>(NT) * 16, true, kMaxWindow);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wattn_bwd_q_kernel<Ops, NW, NT>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wattn_bwd_kv_kernel<Ops, NW, NT>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-    attr = true;
-  }
-  const int Tn = g.ws * g.ws, Tpad = pad_rows<Ops>(Tn);
+  const int Tn = g.ws * g.ws, Tpad = pad_rows<Ops>(Tn), cap = lds_total<Ops>(padded_tiles<Ops>(NT) * 16, true, kMaxWindow);
   const int windows = B * g.nW, slabs = table_slabs(windows, g.nH);
-  hipLaunchKernelGGL((wattn_bwd_q_kernel<Ops, NW, NT>), dim3(slabs * g.nH), dim3(NW * 64),
-                     lds_total<Ops>(Tpad, false, g.ws), st, reinterpret_cast<const T*>(qkv), table,
-                     reinterpret_cast<const T*>(out), reinterpret_cast<const T*>(dout), lse,
-                     reinterpret_cast<T*>(dqkv), ws, g, windows, slabs, scale);
-  PASSL_RETURN_IF_LAUNCH_FAILED();
-  hipLaunchKernelGGL((wattn_bwd_kv_kernel<Ops, NW, NT>), dim3(windows * g.nH), dim3(NW * 64),
-                     lds_total<Ops>(Tpad, true, g.ws), st, reinterpret_cast<const T*>(qkv), table,
-                     reinterpret_cast<const T*>(out), reinterpret_cast<const T*>(dout), lse,
-                     reinterpret_cast<T*>(dqkv), g, scale);
-  PASSL_RETURN_IF_LAUNCH_FAILED();
+  const T *q = reinterpret_cast<const T*>(qkv), *o = reinterpret_cast<const T*>(out), *d = reinterpret_cast<const T*>(dout);
+  int rc = attn::launch_sweep<&wattn_bwd_q_kernel<Ops, NW, NT>, NW>(
+      slabs * g.nH, lds_total<Ops>(Tpad, false, g.ws), cap, st, q, table, o, d, lse, reinterpret_cast<T*>(dqkv), ws, g,
+      windows, slabs, scale);
+  if (rc != PASSL_OK) return rc;
+  rc = attn::launch_sweep<&wattn_bwd_kv_kernel<Ops, NW, NT>, NW>(
+      windows * g.nH, lds_total<Ops>(Tpad, true, g.ws), cap, st, q, table, o, d, lse, reinterpret_cast<T*>(dqkv), g, scale);
+  if (rc != PASSL_OK) return rc;
   const int64_t n = (int64_t)g.nH * Tn * Tn;
   if (slabs > 1) {
     hipLaunchKernelGGL(wattn_slab_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ws, n, slabs);
