@@ -827,6 +827,49 @@ int passl_hip_window_attention_bwd(const void* qkv, const float* table, const vo
 int passl_hip_patch_merge(const void* x, void* y, int B, int H, int W, int C, int dtype, passl_stream_t stream);
 int passl_hip_patch_merge_bwd(const void* dy, void* dx, int B, int H, int W, int C, int dtype, passl_stream_t stream);
 
+/* ---------------------------------------------------------------- CaiT (csrc/cait_attention.hip)
+ * Talking-heads attention.  Reference: TalkingHeadAttn.forward, passl/models/cait.py:137-185.
+ * qkv [B, T, 3, H, DH] in `dtype`; out, dout [B, T, H, DH]; lse fp32 [B, H, T], the log-sum-exp of A_g's rows.
+ * wl [H, H], bl [H] (proj_l) and ww [H, H], bw [H] (proj_w) are fp32, [in, out] as the parameters lie.  Per image:
+ *   S_h = (q_h k_h^T) scale;  A_g = sum_h S_h wl[h, g] + bl[g];  P_g = softmax_j A_g over the T keys;
+ *   R_g = sum_h P_h ww[h, g] + bw[g];  O_g = R_g v_g.
+ * All arithmetic is fp32 on the stored values in both dtypes; bf16 rounds only what it stores.
+ * Accepted: DH = 48, 1 <= T <= 208, 1 <= H <= 8 (PASSL_EUNSUPPORTED otherwise); tensors in `dtype` 16-byte aligned
+ * (PASSL_EINVAL otherwise).  Nothing is launched when a status other than PASSL_OK is returned for these reasons. */
+int passl_hip_talking_heads_attention_fwd(const void* qkv, const float* wl, const float* bl, const float* ww,
+                                          const float* bw, void* out, float* lse, int B, int T, int H, int DH,
+                                          float scale, int dtype, passl_stream_t stream);
+/* dqkv [B, T, 3, H, DH] (fully written); dwl, dww fp32 [H, H] and dbl, dbw fp32 [H] (WRITTEN, summed over the batch).
+ * ws_buf holds delta [B, H, T] (delta_h[i] = sum_j P_h dP_h, written by the dQ sweep and read by the dK / dV sweep) and
+ * one partial [144] of the small gradients per workgroup, added in a fixed order by a last launch: no atomics, two
+ * runs give the same bits.  ws_floats >= PASSL_TALKING_HEADS_ATTENTION_WS_FLOATS(B, T, H). */
+#define PASSL_TALKING_HEADS_ATTENTION_WS_FLOATS(B, T, H) \
+  ((int64_t)(B) * (H) * (T) + (int64_t)(B) * (((T) + 15) / 16) * 144)
+int passl_hip_talking_heads_attention_bwd(const void* qkv, const float* wl, const float* bl, const float* ww,
+                                          const float* bw, const void* dout, const float* lse, void* dqkv, float* dwl,
+                                          float* dbl, float* dww, float* dbw, float* ws_buf, int64_t ws_floats, int B,
+                                          int T, int H, int DH, float scale, int dtype, passl_stream_t stream);
+/* Class attention.  Reference: ClassAttn.forward, cait.py:46-88, after the three Linears.  q, out, dout, dq
+ * [B, H * DH] (the class rows); k, v, dk, dv [B, T, H * DH]; lse fp32 [B, H].  out_h = softmax_j((q_h . k_jh) scale) v_h.
+ * One wave per (image, head); k and v are read once per direction.  Same envelope as above. */
+int passl_hip_class_attention_fwd(const void* q, const void* k, const void* v, void* out, float* lse, int B, int T,
+                                  int H, int DH, float scale, int dtype, passl_stream_t stream);
+int passl_hip_class_attention_bwd(const void* q, const void* k, const void* v, const void* dout, const float* lse,
+                                  void* dq, void* dk, void* dv, int B, int T, int H, int DH, float scale, int dtype,
+                                  passl_stream_t stream);
+/* Token plumbing of the CaiT model over rows of C channels in `dtype` (C % 8 == 0, tensors 16-byte aligned; PASSL_EINVAL
+ * otherwise), one streaming launch each:
+ *   pos_add:    out[b, t] = x[b, t] + pos[t], pos fp32 [L, C]; cait.py:354 (the class row joins later and has no position)
+ *   cls_concat: out [B, 1 + L, C] = concat(c, x) along the token axis, x [B, L, C]; c [B, C], or [C] when c_per_image == 0
+ *               (cait.py:130 and the expand of :360)
+ *   cls_split:  its backward: dc [B, C] = dout[:, 0], dx [B, L, C] = dout[:, 1:] (+ add [B, L, C] unless NULL). */
+int passl_hip_cait_pos_add(const void* x, const float* pos, void* out, int B, int L, int C, int dtype,
+                           passl_stream_t stream);
+int passl_hip_cait_cls_concat(const void* c, int c_per_image, const void* x, void* out, int B, int L, int C, int dtype,
+                              passl_stream_t stream);
+int passl_hip_cait_cls_split(const void* dout, const void* add, void* dc, void* dx, int B, int L, int C, int dtype,
+                             passl_stream_t stream);
+
 /* ---------------------------------------------------------------- mixup / cutmix and soft-target cross-entropy
  * Reference: class Mixup, passl_v110/datasets/preprocess/mixup.py:108-276 (the reference mixes on the host, in numpy or
  * through the framework's CPU tensors); SoftTargetCrossEntropy, tasks/ssl/mae/util/loss.py:44-47. */

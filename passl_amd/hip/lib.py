@@ -138,6 +138,14 @@ SIGNATURES = {
                                              c_f, c_i, c_p]),
     'passl_hip_patch_merge': (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
     'passl_hip_patch_merge_bwd': (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
+    'passl_hip_talking_heads_attention_fwd': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_p]),
+    'passl_hip_talking_heads_attention_bwd': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l,
+                                                    c_i, c_i, c_i, c_i, c_f, c_i, c_p]),
+    'passl_hip_class_attention_fwd': (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_p]),
+    'passl_hip_class_attention_bwd': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_p]),
+    'passl_hip_cait_pos_add': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
+    'passl_hip_cait_cls_concat': (c_i, [c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
+    'passl_hip_cait_cls_split': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
     'passl_hip_quick_gelu_fwd': (c_i, [c_p, c_p, c_l, c_i, c_p]),
     'passl_hip_quick_gelu_bwd': (c_i, [c_p, c_p, c_p, c_l, c_i, c_p]),
     'passl_hip_embed_fwd': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),

@@ -796,6 +796,24 @@ class _ToComputeFn(Function):
         return ops.cast_f32(dy)
 
 
+class _ToF32Fn(Function):
+    """Compute-dtype rows -> fp32 with a HIP cast kernel; the gradient goes back in the rows' dtype."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.dtype = x.dtype
+        return ops.cast_f32(x.contiguous())
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ops.cast_to(dy.contiguous(), ctx.dtype)
+
+
+def to_f32(x):
+    """Widen a compute-dtype activation to fp32 (identity for fp32)."""
+    return x if x.dtype == torch.float32 else _ToF32Fn.apply(x)
+
+
 def to_compute(x, dtype):
     """Cast an fp32 activation to the compute dtype (identity for fp32 compute)."""
     if dtype == torch.float32 or x.dtype == dtype:
@@ -1353,6 +1371,164 @@ def window_attention(qkv, table, B, Hp, Wp, ws, shift, nH, DH, scale):
     from autograd."""
     param_expect_grad(table)
     return _WindowAttentionFn.apply(qkv, table, B, Hp, Wp, ws, shift, nH, DH, float(scale))
+
+
+class _TalkingHeadsAttentionFn(Function):
+    """CaiT's talking-heads attention (csrc/cait_attention.hip) on the fused qkv projection [B*T, 3*H*48]: both Linears
+    over the head axis run inside the kernel.  Backward: dqkv, and the four small gradients WRITTEN into the .grad of
+    arena parameters (returned through autograd for any other tensor)."""
+
+    @staticmethod
+    def forward(ctx, qkv, wl, bl, ww, bw, B, T, H, DH, scale):
+        _need_contiguous('talking_heads_attention', qkv=qkv)
+        out, lse = ops.talking_heads_attention_fwd(qkv, wl.detach(), bl.detach(), ww.detach(), bw.detach(), B, T, H,
+                                                   DH, scale)
+        ctx.save_for_backward(qkv, lse)
+        ctx.mix, ctx.dims = (wl, bl, ww, bw), (B, T, H, DH, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, lse = ctx.saved_tensors
+        mix = ctx.mix
+        from_arena = all(getattr(p, '_passl_arena', None) is not None for p in mix)
+        grads = []
+        for p in mix:
+            g = p.grad if from_arena else None
+            if g is None:
+                g = ops.zeros(*p.shape, dtype=p.dtype, device=p.device)
+                if from_arena:
+                    p.grad = g
+            grads.append(g)
+        dqkv = ops.talking_heads_attention_bwd_into(qkv, *(p.detach() for p in mix), dout.contiguous(), lse, *grads,
+                                                    *ctx.dims)
+        if from_arena:
+            param_grad_ready(*mix)
+            return (dqkv,) + (None,) * 9
+        return (dqkv,) + tuple(grads) + (None,) * 5
+
+
+def talking_heads_attention(qkv, wl, bl, ww, bw, B, T, H, DH, scale):
+    """qkv: rows [B*T, 3*H*DH]; wl, bl / ww, bw: the fp32 proj_l / proj_w weight [H, H] ([in, out]) and bias [H]."""
+    param_expect_grad(wl, bl, ww, bw)
+    return _TalkingHeadsAttentionFn.apply(qkv, wl, bl, ww, bw, B, T, H, DH, float(scale))
+
+
+class _ClassAttentionFn(Function):
+    """CaiT's class attention (csrc/cait_attention.hip): one query per (image, head), the projected class row."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, B, T, H, DH, scale):
+        _need_contiguous('class_attention', q=q, k=k, v=v)
+        out, lse = ops.class_attention_fwd(q, k, v, B, T, H, DH, scale)
+        ctx.save_for_backward(q, k, v, lse)
+        ctx.dims = (B, T, H, DH, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, lse = ctx.saved_tensors
+        return ops.class_attention_bwd(q, k, v, dout.contiguous(), lse, *ctx.dims) + (None,) * 5
+
+
+def class_attention(q, k, v, B, T, H, DH, scale):
+    """q: rows [B, H*DH]; k, v: rows [B*T, H*DH] -> [B, H*DH]."""
+    return _ClassAttentionFn.apply(q, k, v, B, T, H, DH, float(scale))
+
+
+class _PosAddFn(Function):
+    """rows [B*L, C] + pos_embed [1, L, C] (cait.py:354).  Backward: dx is dout; dpos += its column sums over the batch,
+    straight into pos.grad."""
+
+    @staticmethod
+    def forward(ctx, x, pos, B, L):
+        _need_contiguous('pos_add', x=x)
+        ctx.pos, ctx.dims = pos, (B, L)
+        param_expect_grad(pos)
+        return ops.cait_pos_add(x, pos.detach(), B, L)
+
+    @staticmethod
+    def backward(ctx, dout):
+        pos, (B, L) = ctx.pos, ctx.dims
+        if pos.requires_grad:
+            if pos.grad is None:
+                pos.grad = ops.zeros(*pos.shape, dtype=pos.dtype, device=pos.device)
+            ops.colsum_into(dout.contiguous().view(B, -1), pos.grad.view(-1), accumulate=True)
+            param_grad_ready(pos)
+        return dout, None, None, None
+
+
+def pos_add(x, pos, B, L):
+    return _PosAddFn.apply(x, pos, B, L)
+
+
+class _ClsConcatFn(Function):
+    """concat(c, x) along the token axis: rows [B*(L+1), C] whose row 0 of every image is the class row.  ``c`` is rows
+    [B, C], or the fp32 ``cls_token`` parameter (cait.py:360: its expand is an address, its gradient the column sum of
+    the class rows' gradient, added into cls_token.grad).  The patch rows x feed every token-only block: ``slot_in`` /
+    ``slot_out`` chain their gradients through the split launches instead of an add of autograd's.  A block's backward
+    runs before that of the block before it, so the LAST block has slot_out only and the FIRST slot_in only."""
+
+    @staticmethod
+    def forward(ctx, x, c, B, L, slot_in, slot_out):
+        _need_contiguous('cls_concat', x=x, c=c)
+        ctx.cls = c if isinstance(c, tnn.Parameter) else None
+        if ctx.cls is not None:
+            param_expect_grad(c)
+            c = ops.cast_to(c.detach().view(1, -1), x.dtype)
+        if slot_out is not None and ctx.needs_input_grad[0]:
+            slot_out.arm()
+        ctx.dims, ctx.slot_in, ctx.slot_out = (B, L), slot_in, slot_out
+        return ops.cait_cls_concat(c, x, B, L)
+
+    @staticmethod
+    def backward(ctx, dout):
+        B, L = ctx.dims
+        add = ctx.slot_in.take() if (ctx.slot_in is not None and ctx.slot_in.armed) else None
+        dc, dx = ops.cait_cls_split(dout.contiguous(), add, B, L)
+        if ctx.cls is not None:
+            cls = ctx.cls
+            if cls.grad is None:
+                cls.grad = ops.zeros(*cls.shape, dtype=cls.dtype, device=cls.device)
+            ops.colsum_into(dc, cls.grad.view(-1), accumulate=True)
+            param_grad_ready(cls)
+            dc = None
+        if ctx.slot_out is not None and ctx.slot_out.armed:
+            ctx.slot_out.put(dx)
+            dx = None
+        return dx, dc, None, None, None, None
+
+
+def cls_concat(x, c, B, L, slot_in=None, slot_out=None):
+    return _ClsConcatFn.apply(x, c, B, L, slot_in, slot_out)
+
+
+class _ForkFn(Function):
+    """n aliases of rows x whose gradients are added by the library (residual + 1 * branch of csrc/drop_path.hip), not
+    by autograd: a tensor with several consumers inside a step plan."""
+
+    @staticmethod
+    def forward(ctx, x, n, ones, B, T):
+        ctx.save_for_backward(ones)
+        ctx.dims = (B, T)
+        return tuple(x.view(x.shape) for _ in range(n))
+
+    @staticmethod
+    def backward(ctx, *grads):
+        (ones,) = ctx.saved_tensors
+        B, T = ctx.dims
+        acc = None
+        for g in grads:
+            if g is None:
+                continue
+            g = g.contiguous()
+            acc = g if acc is None else ops.drop_path_add(g, acc, ones, 1.0, B, T)
+        return acc, None, None, None, None
+
+
+def fork(x, n, ones, B, T):
+    """ones: fp32 [B] of 1 on the device."""
+    return _ForkFn.apply(x, n, ones, B, T)
 
 
 class _PatchMergeFn(Function):

@@ -830,6 +830,83 @@ def patch_merge_bwd(dy, B, H, W):
     return dx
 
 
+# ------------------------------------------------------------------ CaiT (csrc/cait_attention.hip)
+# the envelope of the two kernels (check_shape): model constructors check it up front
+CAIT_ATTENTION_HEAD_DIM = 48
+CAIT_ATTENTION_MAX_HEADS = 8
+CAIT_ATTENTION_MAX_TOKENS = 208
+
+
+def talking_heads_attention_ws_floats(B, T, H):
+    """include/passl_hip.h: PASSL_TALKING_HEADS_ATTENTION_WS_FLOATS."""
+    return B * H * T + B * ((T + 15) // 16) * 144
+
+
+def talking_heads_attention_fwd(qkv, wl, bl, ww, bw, B, T, H, DH, scale):
+    """qkv [B*T, 3*H*DH]; wl, ww fp32 [H, H] ([in, out]) and bl, bw fp32 [H] -> out [B*T, H*DH], lse fp32 [B, H, T]."""
+    out = torch.empty(B * T, H * DH, dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty(B, H, T, dtype=torch.float32, device=qkv.device)
+    L.check(_lib().passl_hip_talking_heads_attention_fwd(L.ptr(qkv), L.ptr(wl), L.ptr(bl), L.ptr(ww), L.ptr(bw),
+                                                         L.ptr(out), L.ptr(lse), B, T, H, DH, scale, L.dt(qkv),
+                                                         L.stream()), 'talking_heads_attention_fwd')
+    return out, lse
+
+
+def talking_heads_attention_bwd_into(qkv, wl, bl, ww, bw, dout, lse, dwl, dbl, dww, dbw, B, T, H, DH, scale):
+    """-> dqkv; the four fp32 gradients dwl, dbl, dww, dbw are WRITTEN."""
+    dqkv = torch.empty_like(qkv)
+    buf = workspace.get(talking_heads_attention_ws_floats(B, T, H), qkv.device)
+    L.check(_lib().passl_hip_talking_heads_attention_bwd(L.ptr(qkv), L.ptr(wl), L.ptr(bl), L.ptr(ww), L.ptr(bw),
+                                                         L.ptr(dout), L.ptr(lse), L.ptr(dqkv), L.ptr(dwl), L.ptr(dbl),
+                                                         L.ptr(dww), L.ptr(dbw), L.ptr(buf), buf.numel(), B, T, H, DH,
+                                                         scale, L.dt(qkv), L.stream()), 'talking_heads_attention_bwd')
+    return dqkv
+
+
+def class_attention_fwd(q, k, v, B, T, H, DH, scale):
+    """q [B, H*DH] (the class rows), k, v [B*T, H*DH] -> out [B, H*DH], lse fp32 [B, H]."""
+    out = torch.empty(B, H * DH, dtype=q.dtype, device=q.device)
+    lse = torch.empty(B, H, dtype=torch.float32, device=q.device)
+    L.check(_lib().passl_hip_class_attention_fwd(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), L.ptr(lse), B, T, H, DH,
+                                                 scale, L.dt(q), L.stream()), 'class_attention_fwd')
+    return out, lse
+
+
+def class_attention_bwd(q, k, v, dout, lse, B, T, H, DH, scale):
+    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    L.check(_lib().passl_hip_class_attention_bwd(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(dout), L.ptr(lse), L.ptr(dq),
+                                                 L.ptr(dk), L.ptr(dv), B, T, H, DH, scale, L.dt(q), L.stream()),
+            'class_attention_bwd')
+    return dq, dk, dv
+
+
+def cait_pos_add(x, pos, B, Ln):
+    """x rows [B*Ln, C] + pos fp32 [Ln, C] (broadcast over the batch) -> rows [B*Ln, C]."""
+    out = torch.empty_like(x)
+    L.check(_lib().passl_hip_cait_pos_add(L.ptr(x), L.ptr(pos), L.ptr(out), B, Ln, x.shape[-1], L.dt(x), L.stream()),
+             'cait_pos_add')
+    return out
+
+
+def cait_cls_concat(c, x, B, Ln):
+    """c rows [B, C] (or [1, C]: the same class row for every image) and x rows [B*Ln, C] -> rows [B*(Ln+1), C]."""
+    Cc = x.shape[-1]
+    out = torch.empty(B * (Ln + 1), Cc, dtype=x.dtype, device=x.device)
+    L.check(_lib().passl_hip_cait_cls_concat(L.ptr(c), int(c.shape[0] != 1 or B == 1), L.ptr(x), L.ptr(out), B, Ln,
+                                              Cc, L.dt(x), L.stream()), 'cait_cls_concat')
+    return out
+
+
+def cait_cls_split(dout, add, B, Ln):
+    """dout rows [B*(Ln+1), C] -> (dc [B, C], dx [B*Ln, C] = the patch rows, plus `add` when given)."""
+    Cc = dout.shape[-1]
+    dc = torch.empty(B, Cc, dtype=dout.dtype, device=dout.device)
+    dx = torch.empty(B * Ln, Cc, dtype=dout.dtype, device=dout.device)
+    L.check(_lib().passl_hip_cait_cls_split(L.ptr(dout), L.ptr(add), L.ptr(dc), L.ptr(dx), B, Ln, Cc, L.dt(dout),
+                                             L.stream()), 'cait_cls_split')
+    return dc, dx
+
+
 def mae_mask(noise, len_keep):
     B, Ln = noise.shape
     dev = noise.device
