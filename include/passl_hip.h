@@ -150,7 +150,8 @@ int passl_hip_momentum_sgd_dev(float* p, const float* g, float* v, int64_t n, co
 
 /* LARS momentum over a flat fp32 buffer holding many parameter tensors ("segments").
  * The buffer is cut into blocks of at most 4096 elements, each inside ONE segment
- * (blk_off: element offset, 4-aligned; blk_len; blk_seg: segment index); per segment s:
+ * (blk_off: element offset, which MUST be a multiple of 4: with p, g, v 16-byte aligned the kernels read and write
+ * float4 at p + blk_off + 4 i; blk_len; blk_seg: segment index); per segment s:
  *   local_lr = lr*lars_coeff*|p_s| / (|g_s| + wd_s*|p_s| + epsilon)   if wd_s > 0, |p_s| > 0, |g_s| > 0
  *            = lr                                                     otherwise
  *   v = mu*v + local_lr*(g*grad_scale + wd_s*p);   p = p - v

@@ -38,7 +38,8 @@ class _Toy(torch.nn.Module):
 @pytest.mark.parametrize('clip, wd, tc, lr', [(False, 0.0, 0.001, 1.6), (True, 1e-3, 0.02, 0.05), (False, 1e-2, 0.02, 0.3)])
 def test_larc_kernel_matches_the_rule(clip, wd, tc, lr):
     """passl_hip_larc_momentum_dev over an arena of six tensors (one with zero norm: raw gradient, no decay) vs the
-    rule of passl/optimizer/momentum_larc.py restated in fp64, three steps with a changing rate."""
+    rule of passl/optimizer/momentum_larc.py restated in fp64, three steps with a changing rate.  (A norm per tensor:
+    the element-wise float64 bounds are in test_flat_numerics_gpu.py.)"""
     from passl_amd.hip.nn import EncoderArena
     from passl_amd.solver.optimizer import MomentumLARC
     hip_config.set_device('gpu')

@@ -168,6 +168,7 @@ def test_patchify_and_masked_patch_loss():
 
 
 def test_adamw_kernel_vs_oracle_rule():
+    """One size, one loose bound: the element-wise float64 bounds are in test_flat_numerics_gpu.py."""
     gen = torch.Generator().manual_seed(4)
     n = 100003
     p = torch.randn(n, generator=gen); g = torch.randn(n, generator=gen) * 0.1

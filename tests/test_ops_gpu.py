@@ -42,6 +42,7 @@ def nhwc(x):
 # ---------------------------------------------------------------- flat kernels
 @pytest.mark.parametrize('n', [1024, 4099, 3_000_003])
 def test_ema_sgd_cast(n):
+    """Against an fp32 evaluation: the element-wise float64 bounds are in test_flat_numerics_gpu.py."""
     g = torch.Generator().manual_seed(n)
     k = torch.randn(n, generator=g)
     q = torch.randn(n, generator=g)

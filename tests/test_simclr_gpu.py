@@ -93,6 +93,7 @@ def test_ntxent_unnormalised_and_gathered_columns():
 
 
 def test_lars_kernel_vs_oracle_rule():
+    """One table, one set of scalars: the element-wise float64 bounds are in test_flat_numerics_gpu.py."""
     gen = torch.Generator().manual_seed(1)
     sizes = [9408, 64, 64, 4096 * 3 + 40, 8, 2048 * 128]
     offs, total = [], 0
