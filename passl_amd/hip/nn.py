@@ -17,6 +17,7 @@ eps 1e-5, biased running var, ``_use_global_stats``), MaxPool2D(3,2,1), Adaptive
 Linear — as used by passl_v110/modeling/backbones/resnetimagenet.py:111-253 and
 passl_v110/modeling/necks/base_neck.py:68-97.
 """
+import os
 from types import SimpleNamespace
 
 import torch
@@ -1176,6 +1177,129 @@ class DropoutState:
             raise RuntimeError('dropout backward of training pass %d while the model is in pass %d: the step counter '
                                'has moved, the masks would differ from the forward\'s (run each backward before the '
                                'next training forward)' % (ordinal, self.ordinal))
+
+
+def process_rank():
+    """The rank that the seeds of stochastic depth and dropout are offset by: data-parallel ranks draw different masks."""
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized():
+        return dist.get_rank()
+    return int(os.environ.get('RANK', 0))
+
+
+class DropPathState:
+    """The stochastic-depth state of ONE model (csrc/drop_path.hip): the keep table, its row layout, the Philox key and
+    the step counter in device memory.
+
+    ``blocks`` are the blocks that own rows of the table, in row order; each owns ``rows_per_block`` consecutive rows
+    (1: the block's one residual; 2: its attention residual, then its MLP residual) and ``keep_probs`` — one float per
+    row — repeats the block's ``keep_prob`` that often.  ``keep`` — once at the head of every forward — returns the
+    table [len(keep_probs), B] of this pass: one ``passl_hip_drop_path_draw`` launch fills it from (seed, counter) and
+    advances the counter on the device, so a replayed step plan or a captured graph draws a fresh table at every
+    replay.  ``rows`` hands a block its rows of that table.
+
+    A plain object, on purpose: nothing of it is in ``state_dict()`` or broadcast by ``param_sync``.  The counter, the
+    keep-probability vector and one table per batch size are allocated at the first draw and never again (a recorded
+    plan holds their addresses); ``set_seed`` refills the counter in place.  The constructor draws from no generator:
+    the model seeds it from torch's global CPU generator plus the process rank, so ``torch.manual_seed(seed + rank)``
+    reproduces a run and data-parallel ranks draw different masks.  A resumed run restarts the counter at 0."""
+
+    def __init__(self, keep_probs, seed=0, step=0):
+        self.keep_probs = [float(p) for p in keep_probs]
+        self.blocks, self._rows = [], {}
+        self.draws = 0                                    # tables drawn (host counter)
+        self._dp_tables = {}                              # batch size -> keep table [len(keep_probs), B]
+        self._dp_keep_prob = self._dp_step = None         # device state, made at the first draw
+        self.set_seed(seed, step)
+
+    @classmethod
+    def for_blocks(cls, blocks, rows_per_block, seed=0, step=0):
+        self = cls([blk.keep_prob for blk in blocks for _ in range(rows_per_block)], seed, step)
+        self.blocks = list(blocks)
+        for k, blk in enumerate(self.blocks):
+            self._rows[blk] = k if rows_per_block == 1 else slice(rows_per_block * k, rows_per_block * (k + 1))
+        return self
+
+    def set_seed(self, seed, step=0):
+        """Key of the Philox draw and the value of the step counter (the next draw uses it)."""
+        self.seed = int(seed) & ((1 << 64) - 1)
+        self.step0 = int(step)
+        if self._dp_step is not None:
+            self._dp_step.fill_(self.step0 - (1 << 64) if self.step0 >= 1 << 63 else self.step0)
+
+    def step(self):
+        """The counter's value = ``step`` of set_seed plus the draws since (reads the device: synchronises)."""
+        return self.step0 if self._dp_step is None else int(self._dp_step.item()) & ((1 << 64) - 1)
+
+    def table(self, B):
+        """The table that the last draw of batch size B filled, or None."""
+        return self._dp_tables.get(B)
+
+    def keep(self, B, device, given=None):
+        """-> the keep table of one forward pass: ``given`` (an injected table; no draw), or a fresh draw."""
+        shape = (len(self.keep_probs), B)
+        if given is not None:
+            if tuple(given.shape) != shape:
+                raise ValueError('drop_path_keep must be [%d, %d], got %s' % (shape + (tuple(given.shape),)))
+            return given.to(device=device, dtype=torch.float32).contiguous()
+        if self._dp_step is None:
+            self._dp_keep_prob = torch.tensor(self.keep_probs, dtype=torch.float32, device=device)
+            self._dp_step = torch.zeros(1, dtype=torch.int64, device=device)
+            self.set_seed(self.seed, self.step0)
+        keep = self._dp_tables.get(B)
+        if keep is None:
+            keep = self._dp_tables[B] = torch.empty(shape, dtype=torch.float32, device=device)
+        self.draws += 1
+        return ops.drop_path_draw(keep, self._dp_keep_prob, self.seed, self._dp_step)
+
+    def rows(self, keep, blk):
+        """-> the rows of the table ``keep`` that ``blk`` owns ([B] with one row per block, else [rows, B]), or None."""
+        r = self._rows.get(blk)
+        return None if r is None else keep[r]
+
+
+class DropPathModel:
+    """Mixin: the stochastic-depth surface of a model over ``self._drop_path``, a DropPathState, or None when nothing
+    can drop (rate 0).  The model's constructor calls ``_seed_drop_path`` where its seed is drawn."""
+
+    _drop_path = None
+
+    def _seed_drop_path(self, blocks, rows_per_block):
+        """``blocks``: those that own rows of the keep table.  With any, ONE draw from torch's global CPU generator."""
+        blocks = list(blocks)
+        if blocks:
+            seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+            self._drop_path = DropPathState.for_blocks(blocks, rows_per_block, seed + process_rank())
+
+    def set_drop_path_seed(self, seed, step=0):
+        """Key of the Philox draw and the value of the device step counter (the next training forward uses it)."""
+        if self._drop_path is not None:
+            self._drop_path.set_seed(seed, step)
+
+    def drop_path_step(self):
+        """The step counter = the number of draws since set_drop_path_seed (reads the device: synchronises)."""
+        return 0 if self._drop_path is None else self._drop_path.step()
+
+    def drop_path_table(self, B):
+        """The keep table the last training forward of batch size B used (None before the first)."""
+        return None if self._drop_path is None else self._drop_path.table(B)
+
+    @property
+    def drop_path_draws(self):
+        """Training forwards that drew a table (host counter)."""
+        return 0 if self._drop_path is None else self._drop_path.draws
+
+    def _drop_path_keep(self, B, device, given=None):
+        """-> the keep table of this forward pass, or None when nothing can drop (evaluation mode, rate 0)."""
+        if not (self.training and self._drop_path is not None):
+            if given is not None:
+                raise ValueError('drop_path_keep= needs a model in training mode built with drop_path_rate > 0')
+            return None
+        return self._drop_path.keep(B, device, given)
+
+    def _drop_path_rows(self, keep, blk):
+        """-> ``blk``'s rows of this pass's table, or None (no table, or a block that cannot drop)."""
+        return None if keep is None else self._drop_path.rows(keep, blk)
 
 
 class _DropoutFn(Function):

@@ -22,7 +22,7 @@ from torch.autograd import Function
 from ...hip import config, nn, ops
 from ...modules.get_sincos_pe import get_2d_sincos_pos_embed
 from ...modules.vit import (Attention, Block, Identity, Mlp, PatchEmbed, ViTTrunk, _TokensFn,      # noqa: F401
-                            alias_matrix_param, conv_default_normal_, process_rank, to_2tuple, trunc_normal_,
+                            alias_matrix_param, conv_default_normal_, to_2tuple, trunc_normal_,
                             xavier_uniform_)
 from .builder import BACKBONES
 
@@ -179,18 +179,15 @@ class _PatchMeanFn(Function):
         return dx.view(B * (L + 1), D), None, None, None
 
 
-class VisionTransformer(ViTTrunk):
+class VisionTransformer(nn.DropPathModel, ViTTrunk):
     """The fine-tuning ViT of the v110 tree (passl_v110/modeling/backbones/mae.py:190-277): learnable ``cls_token`` /
     ``pos_embed`` (trunc-normal 0.02), pre-norm blocks, final LayerNorm, output = the class token's row.  Same kernels as
     the pre-training encoder above.  ``drop_path_rate`` is stochastic depth with the reference's ladder
     ``linspace(0, rate, depth)`` (:234); element-wise dropout (``drop_rate`` / ``attn_drop_rate``) is not built.
 
-    Stochastic depth state (plain attributes: not in ``state_dict()``, not broadcast by ``param_sync``): the keep table
-    [2 * depth, B] per batch size (row 2i = attention branch of block i, row 2i + 1 = its MLP branch), the device vector
-    of keep probabilities (1.0 for block 0), a device int64 step counter and the seed.  One
-    ``passl_hip_drop_path_draw`` launch per training forward fills the table from (seed, counter) and advances the
-    counter on the device.  The seed comes from torch's global CPU generator at construction plus the process rank, so
-    ``torch.manual_seed(seed + rank)`` reproduces a run and data-parallel ranks draw different masks."""
+    Stochastic depth (``nn.DropPathState``): the keep table is [2 * depth, B] (row 2i = attention branch of block i, row
+    2i + 1 = its MLP branch); with a rate above 0 every block owns its two rows, block 0 with keep probability 1.0.  The
+    seed is drawn at construction in front of the weights."""
 
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=1000, embed_dim=768, depth=12,
                  num_heads=12, mlp_ratio=4., qkv_bias=True, drop_rate=0., attn_drop_rate=0., drop_path_rate=0.,
@@ -216,12 +213,9 @@ class VisionTransformer(ViTTrunk):
                                              act_layer=act_layer, drop_path=dpr[i]) for i in range(depth)])
         self.norm = norm_layer(embed_dim)
         self.drop_path_rate = float(drop_path_rate)
-        self._dp_tables = {}                                   # batch size -> keep table [2 * depth, B]
-        self._dp_keep_prob = self._dp_step = None              # device state, made on first use
-        self._dp_seed = self._dp_step0 = 0
-        if self.drop_path_rate > 0.:
-            seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
-            self.set_drop_path_seed(seed + process_rank())
+        # every block owns two rows when the rate is above 0 (block 0 with keep probability 1.0); the seed is drawn
+        # in front of the weights
+        self._seed_drop_path(self.blocks if self.drop_path_rate > 0. else (), 2)
         trunc_normal_(self.cls_token, std=0.02)
         trunc_normal_(self.pos_embed, std=0.02)
         with torch.no_grad():
@@ -238,44 +232,6 @@ class VisionTransformer(ViTTrunk):
         """What build_optimizer's layer-wise lr decay asks the backbone (passl_v110/solver/builder.py:182), as the
         reference's beit_ft.py:493 answers it; the reference's own MAE_ViT has no such method."""
         return len(self.blocks)
-
-    # -- stochastic depth ------------------------------------------------------------------------------------------
-    def set_drop_path_seed(self, seed, step=0):
-        """Key of the Philox draw and the value of the step counter (tests; a resumed run restarts at step 0)."""
-        self._dp_seed = int(seed) & ((1 << 64) - 1)
-        self._dp_step0 = int(step)
-        if self._dp_step is not None:
-            self._dp_step.fill_(self._dp_step0 - (1 << 64) if self._dp_step0 >= 1 << 63 else self._dp_step0)
-
-    def drop_path_step(self):
-        """The step counter = the number of draws since set_drop_path_seed (reads the device: synchronises)."""
-        return self._dp_step0 if self._dp_step is None else int(self._dp_step.item()) & ((1 << 64) - 1)
-
-    def drop_path_table(self, B):
-        """The keep table [2 * depth, B] the last training forward of batch size B used (None before the first)."""
-        return self._dp_tables.get(B)
-
-    def _drop_path_keep(self, B, device, given=None):
-        """-> the keep table of this forward pass, or None when nothing can drop (eval mode, rate 0)."""
-        if not (self.training and self.drop_path_rate > 0.):
-            if given is not None:
-                raise ValueError('drop_path_keep= needs a model in training mode built with drop_path_rate > 0')
-            return None
-        slots = 2 * len(self.blocks)
-        if given is not None:
-            if tuple(given.shape) != (slots, B):
-                raise ValueError('drop_path_keep must be [2 * depth, B] = [%d, %d], got %s'
-                                 % (slots, B, tuple(given.shape)))
-            return given.to(device=device, dtype=torch.float32).contiguous()
-        if self._dp_step is None:
-            self._dp_keep_prob = torch.tensor([blk.keep_prob for blk in self.blocks for _ in range(2)],
-                                              dtype=torch.float32, device=device)
-            self._dp_step = torch.zeros(1, dtype=torch.int64, device=device)
-            self.set_drop_path_seed(self._dp_seed, self._dp_step0)
-        keep = self._dp_tables.get(B)
-        if keep is None:
-            keep = self._dp_tables[B] = torch.empty(slots, B, dtype=torch.float32, device=device)
-        return ops.drop_path_draw(keep, self._dp_keep_prob, self._dp_seed, self._dp_step)
 
     def _tokens(self, x, drop_path_keep=None):
         keep = self._drop_path_keep(x.shape[0], x.device, drop_path_keep)

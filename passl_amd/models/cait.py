@@ -20,10 +20,9 @@ Names, constructor arguments, sub-layer / state_dict keys and shapes and the ten
     (LayerNorm is per row).  ``global_pool`` 'avg' and '' construct and are refused at the forward.
 
 Stochastic depth: ``dpr = [drop_path_rate] * depth`` (:282), the same rate for every trunk block, two draws per block
-(one per residual) and ``keep_prob = float32(1 - p)``; the token-only blocks have rate 0.  One
-``passl_hip_drop_path_draw`` launch per training forward fills the table [2 * depth, B] from a seed and a device step
-counter (plain attributes: not in ``state_dict()``), so a replayed step plan draws a fresh table.  Evaluation mode and
-rate 0 launch no draw.
+(one per residual) and ``keep_prob = float32(1 - p)``; the token-only blocks have rate 0 and own no row.  The keep table
+(``hnn.DropPathState``) is [2 * depth, B], rows 2k, 2k + 1 the attention and the MLP residual of trunk block k.
+Evaluation mode and rate 0 launch no draw.
 
 Envelope: the kernels take head dimension 48 (every factory's), at most 8 heads and 208 tokens.  The three 224-pixel
 factories (``cait_xxs24_224``, ``cait_xxs36_224``, ``cait_s24_224``) run.  The seven 384- / 448-pixel factories (576 /
@@ -40,12 +39,12 @@ import numpy as np
 import torch
 import torch.nn as tnn
 
-from ..hip import config, ops
+from ..hip import config
 from ..hip import nn as hnn
 from ..hip.nn import EncoderArena
-from ..modules.vit import Mlp, PatchEmbed, conv_default_normal_, process_rank as _process_rank, trunc_normal_
-from ..utils.checkpoint import load_lenient, read_pdparams, save_pdparams
-from .base_model import Model
+from ..modules.vit import Mlp, PatchEmbed, conv_default_normal_, trunc_normal_
+from ..utils.checkpoint import load_lenient, read_pdparams
+from .base_model import ClassifierModel
 
 __all__ = [
     'Cait', 'ClassAttn', 'LayerScaleBlock', 'LayerScaleBlockClassAttn', 'TalkingHeadAttn',
@@ -188,7 +187,9 @@ class LayerScaleBlock(_LayerScale):
         return hnn.layer_scale_add(self.mlp(h), xr, self.gamma_2, k1, self.keep_prob, B, T)
 
 
-class Cait(Model):
+class Cait(hnn.DropPathModel, ClassifierModel):
+    GLOBAL_POOLS = ('', 'token', 'avg')
+
     def __init__(self, img_size=224, patch_size=16, in_chans=3, num_classes=1000, global_pool='token', embed_dim=768,
                  depth=12, num_heads=12, mlp_ratio=4., qkv_bias=True, drop_rate=0., attn_drop_rate=0., drop_path_rate=0.,
                  block_layers=LayerScaleBlock, block_layers_token=LayerScaleBlockClassAttn, patch_layer=PatchEmbed,
@@ -196,7 +197,7 @@ class Cait(Model):
                  mlp_block=Mlp, init_values=1e-4, attn_block_token_only=ClassAttn, mlp_block_token_only=Mlp,
                  depth_token_only=2, mlp_ratio_token_only=4.0, qk_scale=None):
         super().__init__()
-        assert global_pool in ('', 'token', 'avg')
+        assert global_pool in self.GLOBAL_POOLS
         _refuse_dropout('Cait', drop_rate=drop_rate, attn_drop_rate=attn_drop_rate)
         _refuse_qk_scale('Cait', qk_scale)
         if not 0. <= drop_path_rate < 1.:
@@ -239,26 +240,10 @@ class Cait(Model):
         # the token-only blocks hand the patch rows' gradient backwards: block t puts it where block t - 1 takes it
         self._x_slots = [hnn.GradSlot() for _ in range(max(depth_token_only - 1, 0))]
         self._rows = {}
-        # stochastic depth: two slots of the keep table per trunk block (plain attributes, not in state_dict())
-        self._dp_blocks = [blk for blk in self.blocks if blk.drop_path > 0.]
-        self._dp_tables = {}
-        self._dp_keep_prob = self._dp_step = None
-        self._dp_seed = self._dp_step0 = 0
-        self.drop_path_draws = 0                       # training forwards that drew a table (host counter)
-        if self._dp_blocks:
-            # after the weights: a model with stochastic depth initialises as one without
-            seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
-            self.set_drop_path_seed(seed + _process_rank())
+        # stochastic depth: two rows of the keep table per trunk block with p > 0, none for the token-only blocks; the
+        # seed is drawn after the weights (a model with stochastic depth initialises as one without)
+        self._seed_drop_path([blk for blk in self.blocks if blk.drop_path > 0.], 2)
         self.arena_q = EncoderArena(self, trainable=True)
-
-    # ---- runtime state
-    def sync_runtime_state(self):
-        self.arena_q.refresh()
-
-    def load_state_dict(self, state_dict, strict=True):
-        r = super().load_state_dict(state_dict, strict=strict)
-        self.sync_runtime_state()
-        return r
 
     def load_pretrained(self, path, rank=0, finetune=False):
         sd = read_pdparams(path)
@@ -279,66 +264,8 @@ class Cait(Model):
         load_lenient(self, sd, what='pretrained CaiT')
         self.sync_runtime_state()
 
-    def save(self, path, local_rank=0, rank=0):
-        save_pdparams(self, path, rank)
-
     def no_weight_decay(self):
         return {'pos_embed', 'cls_token'}
-
-    def get_classifier(self):
-        return self.head
-
-    def reset_classifier(self, num_classes, global_pool=None):
-        """A new head of ``num_classes`` (None for 0); the arena is laid out again over the new parameter set."""
-        self.num_classes = num_classes
-        if global_pool is not None:
-            assert global_pool in ('', 'token', 'avg')
-            self.global_pool = global_pool
-        self.head = None
-        if num_classes > 0:
-            self.head = hnn.Linear(self.num_features, num_classes)
-            with torch.no_grad():
-                trunc_normal_(self.head.weight, std=.02)
-                self.head.bias.zero_()
-        self.arena_q = EncoderArena(self, trainable=True)
-
-    # ---- stochastic depth
-    def set_drop_path_seed(self, seed, step=0):
-        """Key of the Philox draw and the value of the device step counter (the next training forward uses it)."""
-        self._dp_seed = int(seed) & ((1 << 64) - 1)
-        self._dp_step0 = int(step)
-        if self._dp_step is not None:
-            self._dp_step.fill_(self._dp_step0 - (1 << 64) if self._dp_step0 >= 1 << 63 else self._dp_step0)
-
-    def drop_path_step(self):
-        """The step counter = the number of draws since set_drop_path_seed (reads the device: synchronises)."""
-        return self._dp_step0 if self._dp_step is None else int(self._dp_step.item()) & ((1 << 64) - 1)
-
-    def drop_path_table(self, B):
-        """The keep table [2 x trunk blocks with p > 0, B] the last training forward of batch size B used (None before
-        it); rows 2k, 2k + 1 are the attention and the MLP residual of the k-th such block."""
-        return self._dp_tables.get(B)
-
-    def _drop_path_keep(self, B, device, given=None):
-        if not (self.training and self._dp_blocks):
-            if given is not None:
-                raise ValueError('drop_path_keep= needs a model in training mode built with drop_path_rate > 0')
-            return None
-        slots = 2 * len(self._dp_blocks)
-        if given is not None:
-            if tuple(given.shape) != (slots, B):
-                raise ValueError('drop_path_keep must be [%d, %d], got %s' % (slots, B, tuple(given.shape)))
-            return given.to(device=device, dtype=torch.float32).contiguous()
-        if self._dp_step is None:
-            probs = [blk.keep_prob for blk in self._dp_blocks for _ in range(2)]
-            self._dp_keep_prob = torch.tensor(probs, dtype=torch.float32, device=device)
-            self._dp_step = torch.zeros(1, dtype=torch.int64, device=device)
-            self.set_drop_path_seed(self._dp_seed, self._dp_step0)
-        keep = self._dp_tables.get(B)
-        if keep is None:
-            keep = self._dp_tables[B] = torch.empty(slots, B, dtype=torch.float32, device=device)
-        self.drop_path_draws += 1
-        return ops.drop_path_draw(keep, self._dp_keep_prob, self._dp_seed, self._dp_step)
 
     # ---- forward
     def _batch_rows(self, B, L, device):
@@ -357,13 +284,8 @@ class Cait(Model):
         B, L = x.shape[0], self.patch_embed.num_patches
         keep = self._drop_path_keep(B, x.device, drop_path_keep)
         x = hnn.pos_add(self.patch_embed(x), self.pos_embed, B, L)
-        slot = 0
         for blk in self.blocks:
-            if keep is not None and blk.drop_path > 0.:
-                x = blk(x, B, L, keep[slot:slot + 2])
-                slot += 2
-            else:
-                x = blk(x, B, L)
+            x = blk(x, B, L, self._drop_path_rows(keep, blk))
         cls_rows, ones = self._batch_rows(B, L, x.device)
         x_cls = self.cls_token
         n = len(self.blocks_token_only)

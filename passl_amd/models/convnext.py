@@ -15,10 +15,8 @@ Names, constructor arguments, sub-layer / state_dict keys and the factories are 
   * global average pool, final LayerNorm and the fp32 head as in the other classifiers.
 
 Stochastic depth: the ladder is ``linspace(0, drop_path_rate, sum(depths))`` in fp32 (:145-147) and
-``keep_prob = float32(1 - p)``.  One ``passl_hip_drop_path_draw`` launch per training forward fills a keep table
-[blocks with p > 0, B] from a seed and a device step counter (plain attributes: not in ``state_dict()``), so
-``torch.manual_seed(seed + rank)`` reproduces a run and a replayed step plan draws a fresh table.  Evaluation mode and
-rate 0 launch no draw and pass no table.
+``keep_prob = float32(1 - p)``.  The keep table (``hnn.DropPathState``) is [blocks with p > 0, B]: one row per such
+block, in network order.  Evaluation mode and rate 0 launch no draw and pass no table.
 
 Initialisation (:163-170): trunc-normal(0.02) weights and zero biases for every convolution and Linear, LayerNorm
 (1, 0), ``gamma`` = ``layer_scale_init_value``, the head scaled by ``head_init_scale``.
@@ -32,8 +30,8 @@ import torch.nn as tnn
 from ..hip import config, ops
 from ..hip import nn as hnn
 from ..hip.nn import EncoderArena
-from ..modules.vit import _PatchProj, process_rank as _process_rank, trunc_normal_
-from ..utils.checkpoint import load_lenient, read_pdparams, save_pdparams
+from ..modules.vit import _PatchProj, trunc_normal_
+from ..utils.checkpoint import load_lenient, read_pdparams
 from .base_model import Model
 
 __all__ = ['ConvNeXt', 'convnext_tiny', 'convnext_small', 'convnext_base', 'convnext_large', 'convnext_xlarge']
@@ -72,7 +70,7 @@ class Block(hnn.Layer):
         return out.view(N, H, W, C)
 
 
-class ConvNeXt(Model):
+class ConvNeXt(hnn.DropPathModel, Model):
     """ConvNeXt (A ConvNet for the 2020s, https://arxiv.org/pdf/2201.03545.pdf)."""
 
     def __init__(self, in_chans=3, class_num=1000, depths=[3, 3, 9, 3], dims=[96, 192, 384, 768], drop_path_rate=0.,
@@ -114,76 +112,16 @@ class ConvNeXt(Model):
                     m.bias.zero_()
             self.head.weight.mul_(head_init_scale)
             self.head.bias.mul_(head_init_scale)
-        # stochastic depth: one slot of the keep table per block that can drop (plain attributes, not in state_dict())
-        self._blocks = [blk for stage in self.stages for blk in stage]
-        self._dp_slot = {}
-        for blk in self._blocks:
-            if blk.drop_path > 0.:
-                self._dp_slot[id(blk)] = len(self._dp_slot)
-        self._dp_tables = {}
-        self._dp_keep_prob = self._dp_step = None
-        self._dp_seed = self._dp_step0 = 0
-        self.drop_path_draws = 0                       # training forwards that drew a table (host counter)
-        if self._dp_slot:
-            # after the weights: a model with stochastic depth initialises as one without
-            seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
-            self.set_drop_path_seed(seed + _process_rank())
+        # stochastic depth: one row of the keep table per block with p > 0; the seed is drawn after the weights (a model
+        # with stochastic depth initialises as one without)
+        self._seed_drop_path([blk for stage in self.stages for blk in stage if blk.drop_path > 0.], 1)
         self.arena_q = EncoderArena(self, trainable=True)
-
-    # ---- runtime state
-    def sync_runtime_state(self):
-        self.arena_q.refresh()
-
-    def load_state_dict(self, state_dict, strict=True):
-        r = super().load_state_dict(state_dict, strict=strict)
-        self.sync_runtime_state()
-        return r
 
     def load_pretrained(self, path, rank=0, finetune=False):
         sd = read_pdparams(path)
         if not finetune:                               # convnext.py:198-199
             load_lenient(self, sd, what='pretrained ConvNeXt')
             self.sync_runtime_state()
-
-    def save(self, path, local_rank=0, rank=0):
-        save_pdparams(self, path, rank)
-
-    # ---- stochastic depth
-    def set_drop_path_seed(self, seed, step=0):
-        """Key of the Philox draw and the value of the device step counter (the next training forward uses it)."""
-        self._dp_seed = int(seed) & ((1 << 64) - 1)
-        self._dp_step0 = int(step)
-        if self._dp_step is not None:
-            self._dp_step.fill_(self._dp_step0 - (1 << 64) if self._dp_step0 >= 1 << 63 else self._dp_step0)
-
-    def drop_path_step(self):
-        """The step counter = the number of draws since set_drop_path_seed (reads the device: synchronises)."""
-        return self._dp_step0 if self._dp_step is None else int(self._dp_step.item()) & ((1 << 64) - 1)
-
-    def drop_path_table(self, B):
-        """The keep table [blocks with p > 0, B] the last training forward of batch size B used (None before it)."""
-        return self._dp_tables.get(B)
-
-    def _drop_path_keep(self, B, device, given=None):
-        if not (self.training and self._dp_slot):
-            if given is not None:
-                raise ValueError('drop_path_keep= needs a model in training mode built with drop_path_rate > 0')
-            return None
-        slots = len(self._dp_slot)
-        if given is not None:
-            if tuple(given.shape) != (slots, B):
-                raise ValueError('drop_path_keep must be [%d, %d], got %s' % (slots, B, tuple(given.shape)))
-            return given.to(device=device, dtype=torch.float32).contiguous()
-        if self._dp_step is None:
-            self._dp_keep_prob = torch.tensor([blk.keep_prob for blk in self._blocks if blk.drop_path > 0.],
-                                              dtype=torch.float32, device=device)
-            self._dp_step = torch.zeros(1, dtype=torch.int64, device=device)
-            self.set_drop_path_seed(self._dp_seed, self._dp_step0)
-        keep = self._dp_tables.get(B)
-        if keep is None:
-            keep = self._dp_tables[B] = torch.empty(slots, B, dtype=torch.float32, device=device)
-        self.drop_path_draws += 1
-        return ops.drop_path_draw(keep, self._dp_keep_prob, self._dp_seed, self._dp_step)
 
     # ---- forward
     @staticmethod
@@ -208,8 +146,7 @@ class ConvNeXt(Model):
                 x = conv(norm(x.view(B * h * w, self.dims[i - 1])).view(B, h, w, self.dims[i - 1]))
                 h, w = h // 2, w // 2
             for blk in self.stages[i]:
-                slot = self._dp_slot.get(id(blk))
-                x = blk(x, keep[slot] if (keep is not None and slot is not None) else None)
+                x = blk(x, self._drop_path_rows(keep, blk))
         return self.norm(self.pool(x))                  # global average pooling, [N, H, W, C] -> [N, C]
 
     def forward(self, x, drop_path_keep=None):

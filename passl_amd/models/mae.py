@@ -17,7 +17,7 @@ import torch
 from ..hip import nn as hnn
 from ..hip.nn import EncoderArena
 from ..modeling.backbones.mae import MAE as _HipMAE
-from ..utils.checkpoint import load_pdparams, save_pdparams
+from ..utils.checkpoint import load_pdparams
 from .base_model import Model
 from .vision_transformer import VisionTransformer
 
@@ -43,14 +43,6 @@ class MaskedAutoencoderViT(_HipMAE, Model):
             self.mask_token.copy_(torch.randn(self.mask_token.shape) * 0.02)
         self.arena_q = EncoderArena(self, trainable=True)         # flat parameters / gradients (AdamW, DP reducer)
 
-    def sync_runtime_state(self):
-        self.arena_q.refresh()
-
-    def load_state_dict(self, state_dict, strict=True):
-        r = super().load_state_dict(state_dict, strict=strict)
-        self.sync_runtime_state()
-        return r
-
     def forward(self, imgs, mask_ratio=0.75, noise=None):
         """-> (loss, pred [N, L, p*p*3], mask [N, L]).  ``noise``: inject the per-sample masking noise (tests)."""
         self.arena_q.refresh()                                   # compute-dtype copies of the updated weights
@@ -58,9 +50,6 @@ class MaskedAutoencoderViT(_HipMAE, Model):
 
     def load_pretrained(self, path, rank=0, finetune=False):
         load_pdparams(self, path, what='pretrained MAE', bare_ok=True)
-
-    def save(self, path, local_rank=0, rank=0):
-        save_pdparams(self, path, rank)
 
 
 class MAEVisionTransformer(VisionTransformer):

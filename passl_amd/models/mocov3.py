@@ -173,11 +173,6 @@ class MoCoV3LinearProbe(MoCoV3ViT, Model):
         self.arena_k.refresh()
         self.arena_q.refresh()
 
-    def load_state_dict(self, state_dict, strict=True):
-        r = super().load_state_dict(state_dict, strict=strict)
-        self.sync_runtime_state()
-        return r
-
     def load_pretrained(self, path, rank=0, finetune=False):
         sd = read_pdparams(path)
         if finetune:
@@ -185,9 +180,6 @@ class MoCoV3LinearProbe(MoCoV3ViT, Model):
                                       'fine-tuning recipe')
         load_lenient(self, sd, what='pretrained model')
         self.sync_runtime_state()
-
-    def save(self, path, local_rank=0, rank=0):
-        save_pdparams(self, path, rank)
 
     def forward(self, x):
         self.arena_q.refresh()
@@ -264,11 +256,6 @@ class MoCoV3Pretrain(Model):
         for a in self._arenas():
             a.refresh()
         self.momentum_encoder.sync_steps()
-
-    def load_state_dict(self, state_dict, strict=True):
-        r = super().load_state_dict(state_dict, strict=strict)
-        self.sync_runtime_state()
-        return r
 
     # -- reference API ---------------------------------------------------------------------------------------
     def contrastive_loss(self, q, k):

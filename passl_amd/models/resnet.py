@@ -13,7 +13,7 @@ import torch
 
 from ..hip import nn as hnn
 from ..modeling.backbones.resnet import BottleneckBlock, ResNet as _Trunk
-from ..utils.checkpoint import load_pdparams, save_pdparams
+from ..utils.checkpoint import load_pdparams
 from .base_model import Model
 
 __all__ = ['ResNet', 'BottleneckBlock', 'resnet50']
@@ -53,9 +53,6 @@ class ResNet(_Trunk, Model):
 
     def load_pretrained(self, path, rank=0, finetune=False):
         load_pdparams(self, path)
-
-    def save(self, path, local_rank=0, rank=0):
-        save_pdparams(self, path, rank)
 
 
 def resnet50(**kwargs):

@@ -84,11 +84,6 @@ class SimSiamPretain(Model):
         self.arena_q.refresh()
         self.arena_p.refresh()
 
-    def load_state_dict(self, state_dict, strict=True):
-        r = super().load_state_dict(state_dict, strict=strict)
-        self.sync_runtime_state()
-        return r
-
     # -- reference API
     def _view(self, x):
         y = _Trunk.forward(self.encoder, x)                  # trunk + average pool (NHWC [N, 1, 1, 2048])
@@ -146,11 +141,6 @@ class SimSiamLinearProbe(ResNet):
         self.arena_k.refresh()
         self.arena_k.update_bn_affine()
         self.arena_q.refresh()
-
-    def load_state_dict(self, state_dict, strict=True):
-        r = super().load_state_dict(state_dict, strict=strict)
-        self.sync_runtime_state()
-        return r
 
     def forward(self, x):
         self.arena_q.refresh()                  # compute-dtype classifier operands from the fp32 masters

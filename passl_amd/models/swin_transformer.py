@@ -19,10 +19,9 @@ The block's window rule is the reference's: ``min(input_resolution) <= window_si
 ``min(input_resolution)`` and shift 0; shifts alternate 0, ``window_size // 2``.
 
 Stochastic depth: the ladder is ``np.linspace(0, drop_path_rate, sum(depths))`` (:537) and ``keep_prob =
-float32(1 - p)``.  The reference draws once per residual, so a block owns TWO slots of the keep table.  One
-``passl_hip_drop_path_draw`` launch per training forward fills the table [2 x blocks with p > 0, B] from a seed and a
-device step counter (plain attributes: not in ``state_dict()``), so a replayed step plan draws a fresh table.
-Evaluation mode and rate 0 launch no draw.
+float32(1 - p)``.  The reference draws once per residual, so a block owns TWO rows of the keep table
+(``hnn.DropPathState``): the table is [2 x blocks with p > 0, B], rows 2k, 2k + 1 the attention and the MLP residual of
+the k-th such block.  Evaluation mode and rate 0 launch no draw.
 
 Initialisation (:565-577): trunc-normal(0.02) Linear weights and bias tables, zero biases, LayerNorm (1, 0); the patch
 convolution keeps Paddle's default (Normal(0, sqrt(2 / fan_in)), zero bias).
@@ -37,10 +36,9 @@ import torch.nn as tnn
 from ..hip import config, ops
 from ..hip import nn as hnn
 from ..hip.nn import EncoderArena
-from ..modules.vit import (Mlp, PatchEmbed, conv_default_normal_, process_rank as _process_rank, to_2tuple,
-                           trunc_normal_)
-from ..utils.checkpoint import load_lenient, read_pdparams, save_pdparams
-from .base_model import Model
+from ..modules.vit import Mlp, PatchEmbed, conv_default_normal_, to_2tuple, trunc_normal_
+from ..utils.checkpoint import load_lenient, read_pdparams
+from .base_model import ClassifierModel
 
 __all__ = [
     'SwinTransformer',
@@ -223,7 +221,7 @@ class BasicLayer(hnn.Layer):
             self.downsample = downsample(input_resolution, dim=dim, out_dim=out_dim, norm_layer=norm_layer)
 
 
-class SwinTransformer(Model):
+class SwinTransformer(hnn.DropPathModel, ClassifierModel):
     """Swin Transformer: Hierarchical Vision Transformer using Shifted Windows, https://arxiv.org/pdf/2103.14030."""
 
     def __init__(self, img_size=224, patch_size=4, in_chans=3, num_classes=1000, global_pool='avg', embed_dim=96,
@@ -231,7 +229,7 @@ class SwinTransformer(Model):
                  qkv_bias=True, drop_rate=0., attn_drop_rate=0., drop_path_rate=0.1, norm_layer=hnn.LayerNorm, ape=False,
                  patch_norm=True, weight_init='', **kwargs):
         super().__init__()
-        assert global_pool in ('', 'avg')
+        assert global_pool in self.GLOBAL_POOLS
         if drop_rate != 0. or attn_drop_rate != 0.:
             raise NotImplementedError('SwinTransformer(drop_rate=%r, attn_drop_rate=%r): dropout is not built for Swin '
                                       '(no config or factory sets it)' % (drop_rate, attn_drop_rate))
@@ -283,37 +281,15 @@ class SwinTransformer(Model):
                     trunc_normal_(m.relative_position_bias_table, std=.02)
             conv_default_normal_(self.patch_embed.proj.weight)        # Paddle's default for nn.Conv2D
             self.patch_embed.proj.bias.zero_()
-        # stochastic depth: two slots of the keep table per block that can drop (plain attributes, not in state_dict())
+        # stochastic depth: two rows of the keep table per block with p > 0; the seed is drawn after the weights (a
+        # model with stochastic depth initialises as one without)
         self._blocks = [blk for layer in self.layers for blk in layer.blocks]
-        self._dp_slot = {}
-        for blk in self._blocks:
-            if blk.drop_path > 0.:
-                self._dp_slot[id(blk)] = 2 * len(self._dp_slot)
-        self._dp_tables = {}
-        self._dp_keep_prob = self._dp_step = None
-        self._dp_seed = self._dp_step0 = 0
-        self.drop_path_draws = 0                       # training forwards that drew a table (host counter)
-        if self._dp_slot:
-            # after the weights: a model with stochastic depth initialises as one without
-            seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
-            self.set_drop_path_seed(seed + _process_rank())
+        self._seed_drop_path([blk for blk in self._blocks if blk.drop_path > 0.], 2)
         self.arena_q = EncoderArena(self, trainable=True)
-
-    # ---- runtime state
-    def sync_runtime_state(self):
-        self.arena_q.refresh()
-
-    def load_state_dict(self, state_dict, strict=True):
-        r = super().load_state_dict(state_dict, strict=strict)
-        self.sync_runtime_state()
-        return r
 
     def load_pretrained(self, path, rank=0, finetune=False):
         load_lenient(self, read_pdparams(path), what='pretrained Swin')        # swin_transformer.py:627-642
         self.sync_runtime_state()
-
-    def save(self, path, local_rank=0, rank=0):
-        save_pdparams(self, path, rank)
 
     def no_weight_decay(self):
         nwd = {'absolute_pos_embed'}
@@ -331,61 +307,6 @@ class SwinTransformer(Model):
                 (r'^norm', (99999, )),
             ])
 
-    def get_classifier(self):
-        return self.head
-
-    def reset_classifier(self, num_classes, global_pool=None):
-        """A new head of ``num_classes`` (None for 0); the arena is laid out again over the new parameter set."""
-        self.num_classes = num_classes
-        if global_pool is not None:
-            assert global_pool in ('', 'avg')
-            self.global_pool = global_pool
-        self.head = None
-        if num_classes > 0:
-            self.head = hnn.Linear(self.num_features, num_classes)
-            with torch.no_grad():
-                trunc_normal_(self.head.weight, std=.02)
-                self.head.bias.zero_()
-        self.arena_q = EncoderArena(self, trainable=True)
-
-    # ---- stochastic depth
-    def set_drop_path_seed(self, seed, step=0):
-        """Key of the Philox draw and the value of the device step counter (the next training forward uses it)."""
-        self._dp_seed = int(seed) & ((1 << 64) - 1)
-        self._dp_step0 = int(step)
-        if self._dp_step is not None:
-            self._dp_step.fill_(self._dp_step0 - (1 << 64) if self._dp_step0 >= 1 << 63 else self._dp_step0)
-
-    def drop_path_step(self):
-        """The step counter = the number of draws since set_drop_path_seed (reads the device: synchronises)."""
-        return self._dp_step0 if self._dp_step is None else int(self._dp_step.item()) & ((1 << 64) - 1)
-
-    def drop_path_table(self, B):
-        """The keep table [2 x blocks with p > 0, B] the last training forward of batch size B used (None before it);
-        rows 2k, 2k + 1 are the attention and the MLP residual of the k-th such block."""
-        return self._dp_tables.get(B)
-
-    def _drop_path_keep(self, B, device, given=None):
-        if not (self.training and self._dp_slot):
-            if given is not None:
-                raise ValueError('drop_path_keep= needs a model in training mode built with drop_path_rate > 0')
-            return None
-        slots = 2 * len(self._dp_slot)
-        if given is not None:
-            if tuple(given.shape) != (slots, B):
-                raise ValueError('drop_path_keep must be [%d, %d], got %s' % (slots, B, tuple(given.shape)))
-            return given.to(device=device, dtype=torch.float32).contiguous()
-        if self._dp_step is None:
-            probs = [blk.keep_prob for blk in self._blocks if blk.drop_path > 0. for _ in range(2)]
-            self._dp_keep_prob = torch.tensor(probs, dtype=torch.float32, device=device)
-            self._dp_step = torch.zeros(1, dtype=torch.int64, device=device)
-            self.set_drop_path_seed(self._dp_seed, self._dp_step0)
-        keep = self._dp_tables.get(B)
-        if keep is None:
-            keep = self._dp_tables[B] = torch.empty(slots, B, dtype=torch.float32, device=device)
-        self.drop_path_draws += 1
-        return ops.drop_path_draw(keep, self._dp_keep_prob, self._dp_seed, self._dp_step)
-
     # ---- forward
     def forward_features(self, x, drop_path_keep=None):
         """-> the normalised rows [B*L, num_features] of the last stage."""
@@ -394,8 +315,7 @@ class SwinTransformer(Model):
         x = self.patch_embed(x)
         for layer in self.layers:
             for blk in layer.blocks:
-                slot = self._dp_slot.get(id(blk))
-                x = blk(x, B, keep[slot:slot + 2] if (keep is not None and slot is not None) else None)
+                x = blk(x, B, self._drop_path_rows(keep, blk))
             if layer.downsample is not None:
                 x = layer.downsample(x, B)
         return self.norm(x)

@@ -28,7 +28,7 @@ from ..hip import nn as hnn
 from ..hip.nn import EncoderArena
 from ..modules.vit import (Attention, Block, Mlp, PatchEmbed, ViTTrunk, conv_default_normal_,      # noqa: F401
                            process_rank as _process_rank, to_2tuple, xavier_uniform_)   # (the reference's names)
-from ..utils.checkpoint import load_lenient, read_pdparams, save_pdparams
+from ..utils.checkpoint import load_lenient, read_pdparams
 from .base_model import Model
 
 __all__ = [
@@ -108,9 +108,6 @@ class VisionTransformer(ViTTrunk, Model):
             self.set_dropout_seed(seed + _process_rank())
         self.arena_q = EncoderArena(self, trainable=True)
 
-    def sync_runtime_state(self):
-        self.arena_q.refresh()
-
     # ---- element-wise dropout
     def set_dropout_seed(self, seed, step=0):
         """Key of the Philox masks and the value of the step counter; the next training forward uses ``step + 1``."""
@@ -121,11 +118,6 @@ class VisionTransformer(ViTTrunk, Model):
     def dropout_step(self):
         """The step counter = ``step`` of set_dropout_seed plus the training forwards since (reads the device)."""
         return 0 if self._dropout is None else self._dropout.step()
-
-    def load_state_dict(self, state_dict, strict=True):
-        r = super().load_state_dict(state_dict, strict=strict)
-        self.sync_runtime_state()
-        return r
 
     def forward_features(self, x):
         if self._dropout is not None and self.training:
@@ -156,9 +148,6 @@ class VisionTransformer(ViTTrunk, Model):
                 sd['pos_embed'] = torch.cat([pos[:, :extra], tok.permute(0, 2, 3, 1).flatten(1, 2)], dim=1).numpy()
         load_lenient(self, sd, what='pretrained ViT')
         self.sync_runtime_state()
-
-    def save(self, path, local_rank=0, rank=0):
-        save_pdparams(self, path, rank)
 
 
 def ViT_base_patch16_224(**kwargs):

@@ -13,7 +13,6 @@ tensor equal to that matrix and becomes the kernels' causal flag; any other mask
 A tower keeps what really differs: parameter names and registration order, its init rule, sin-cos buffer versus
 learnable position table, its head.  ``ViTTrunk`` holds the steps they share."""
 import math
-import os
 
 import numpy as np
 import torch
@@ -28,12 +27,7 @@ def to_2tuple(x):
     return tuple(x) if isinstance(x, (tuple, list)) else (x, x)
 
 
-def process_rank():
-    """The rank that the seeds of stochastic depth and dropout are offset by: data-parallel ranks draw different masks."""
-    import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized():
-        return dist.get_rank()
-    return int(os.environ.get('RANK', 0))
+process_rank = nn.process_rank          # (the towers take it from here)
 
 
 class Identity(nn.Layer):
@@ -356,13 +350,14 @@ class ViTTrunk(nn.Layer):
         return _TokensFn.apply(x, cls, pos, ids, ids, B, L), cls_rows, B, L
 
     def run_blocks(self, x, B, T, keep=None):
-        """``keep``: the stochastic-depth table [2 * depth, B] (rows 2i, 2i + 1 belong to block i), or None."""
+        """``keep``: the stochastic-depth table of this pass (a tower with nn.DropPathModel hands each block its two
+        rows of it), or None."""
         if keep is None:
             for blk in self.blocks:
                 x = blk(x, B, T)
         else:
-            for i, blk in enumerate(self.blocks):
-                x = blk(x, B, T, keep[2 * i:2 * i + 2])
+            for blk in self.blocks:
+                x = blk(x, B, T, self._drop_path_rows(keep, blk))
         return x
 
     def cls_features(self, x, cls_rows, norm):

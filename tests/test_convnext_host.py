@@ -75,7 +75,8 @@ def test_drop_path_ladder_is_the_fixtures():
         assert [b.drop_path for b in blocks] == model.dp_rates
         _rates, keep_prob = MU.ladder(rate)
         assert [b.keep_prob for b in blocks if b.drop_path > 0] == keep_prob
-        assert len(model._dp_slot) == (4 if rate else 0)
+        owners = model._drop_path.blocks if model._drop_path is not None else []
+        assert len(owners) == (4 if rate else 0)
         if rate:
             assert fx['s0_keep'].shape == (4, MU.BATCH) and set(np.unique(fx['s0_keep'])) <= {0.0, 1.0}
 

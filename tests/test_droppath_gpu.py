@@ -316,7 +316,7 @@ def test_eval_mode_and_rate_zero_keep_the_fused_path(monkeypatch):
     out = plain(x, y, mode='train')
     out['loss'].backward()
     assert not calls_p and plain.backbone.drop_path_step() == 0 and plain.backbone.drop_path_table(8) is None
-    assert plain.backbone._dp_step is None
+    assert plain.backbone._drop_path is None                  # no state at all, so no device tensor either
     # a table of the wrong shape is refused before anything is launched
     with pytest.raises(ValueError):
         dropper(x, y, mode='train', drop_path_keep=torch.ones(6, 8, device=DEV))
@@ -342,7 +342,7 @@ def _three_steps(seed):
         losses.append(out['loss'].detach().clone().reshape(1))
         tables.append(model.backbone.drop_path_table(8).clone())
     assert model.backbone.drop_path_step() == 3
-    return torch.cat(losses).cpu(), torch.stack(tables).cpu(), model.backbone._dp_seed
+    return torch.cat(losses).cpu(), torch.stack(tables).cpu(), model.backbone._drop_path.seed
 
 
 def test_same_seed_same_masks_and_losses():

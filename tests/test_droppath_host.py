@@ -93,7 +93,7 @@ def test_seed_follows_the_global_generator_and_the_rank(monkeypatch):
         else:
             monkeypatch.setenv('RANK', str(rank))
         torch.manual_seed(manual)
-        return MAE_ViT(drop_path_rate=0.2, **SMALL)._dp_seed
+        return MAE_ViT(drop_path_rate=0.2, **SMALL)._drop_path.seed
     a = seed_of(3)
     assert a == seed_of(3) and a != seed_of(4)
     assert seed_of(3, rank=2) == (a + 2) & (2 ** 64 - 1)          # an unseeded run: ranks still differ
@@ -104,7 +104,7 @@ def test_seed_follows_the_global_generator_and_the_rank(monkeypatch):
     assert torch.equal(w0, MAE_ViT(drop_path_rate=0., **SMALL).pos_embed.detach())
     m = MAE_ViT(drop_path_rate=0.2, **SMALL)
     m.set_drop_path_seed(12345, step=7)
-    assert m._dp_seed == 12345 and m.drop_path_step() == 7
+    assert m._drop_path.seed == 12345 and m.drop_path_step() == 7
 
 
 def test_droppath_yaml_loads_and_builds():
