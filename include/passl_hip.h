@@ -871,6 +871,42 @@ int passl_hip_cait_cls_concat(const void* c, int c_per_image, const void* x, voi
 int passl_hip_cait_cls_split(const void* dout, const void* add, void* dc, void* dx, int B, int L, int C, int dtype,
                              passl_stream_t stream);
 
+/* ---------------------------------------------------------------- token merging, ToMe (csrc/tome.hip)
+ * Reference: passl/models/utils/tome.py — bipartite_soft_matching :28-118, merge_wavg :121-133, ToMeAttention :172-195.
+ *
+ * Matching.  qkv [B, T, 3, H, DH] in `dtype`, the projection the attention kernel reads.  metric[t] = the mean over
+ * heads of the K slice (k.mean(1)), formed and L2-normalised in fp32.  A = the even tokens (ceil(T/2), token 0 is the
+ * class token), B = the odd tokens (floor(T/2)).  For A row i: node_max[i], node_idx[i] = max and arg-max over B of
+ * metric[2i] . metric[2j+1]; row 0 is -inf / 0 (the class token is never merged, tome.py:63-64).  The r rows of largest
+ * node_max are merged into their arg-max B token.
+ *   Ties (ours; the reference's argsort is not stable): the arg-max is the LOWEST B index of equal scores; of equal
+ *   node_max the LOWER A index ranks first.  A key that is all zero has metric 0 (the reference: NaN).
+ * dest int32 [B, T] = the output row, 0 .. T-r-1, of every input token, in the reference's output order (tome.py:76-78,
+ * 99): the unmerged A tokens in ascending order (the class token stays row 0), then every B token in order; a merged A
+ * token has the row of its B token.  node_max fp32 [B, ceil(T/2)] and node_idx int32 [B, ceil(T/2)] are written unless
+ * NULL.  One launch, one workgroup per image; the score matrix never reaches memory.
+ * Accepted: 3 <= T <= 208, DH in {32, 64} (PASSL_EUNSUPPORTED otherwise); 1 <= r <= (T-1)/2, the clamp of tome.py:53
+ * with the class token protected, qkv 16-byte aligned (PASSL_EINVAL otherwise: the caller clamps, and does not call with
+ * r = 0). */
+int passl_hip_tome_match(const void* qkv, int32_t* dest, float* node_max, int32_t* node_idx, int B, int T, int H, int DH,
+                         int r, int dtype, passl_stream_t stream);
+/* merge_wavg: y[b, row] = sum over {t : dest[b, t] = row} of size[b, t] x[b, t] / size_out[b, row], size_out[b, row] =
+ * the sum of those size[b, t].  x [B, T, C], y [B, T-r, C] in `dtype`; size fp32 [B, T] or NULL (all ones); size_out fp32
+ * [B, T-r]; logsize_out fp32 [B, T-r] = log(size_out) unless NULL (the key bias of the next proportional attention).
+ * fp32 sums in ascending t, one rounding at the store; a gather per output row: no atomics, no scratch, two runs give the
+ * same bits.  A dest outside [0, T-r) is ignored.  1 <= r < T <= 208, C % 8 == 0, x and y 16-byte aligned. */
+int passl_hip_tome_merge_fwd(const void* x, const float* size, const int32_t* dest, void* y, float* size_out,
+                             float* logsize_out, int B, int T, int r, int C, int dtype, passl_stream_t stream);
+/* dx[b, t] = dy[b, dest[b, t]] * (size[b, t] / size_out[b, dest[b, t]]), fully written; the matching and the sizes carry no
+ * gradient (the reference matches under no_grad). */
+int passl_hip_tome_merge_bwd(const void* dy, const float* size, const float* size_out, const int32_t* dest, void* dx,
+                             int B, int T, int r, int C, int dtype, passl_stream_t stream);
+/* Proportional attention, forward only (tome.py:183-185): passl_hip_attention_fwd without the causal flag and with
+ * score = (q . k) scale + key_bias[b, j], key_bias fp32 [B, T] = log(size).  Same envelope, same routing by dtype and
+ * options; with key_bias = 0 the output has the bits of passl_hip_attention_fwd. */
+int passl_hip_attention_fwd_keybias(const void* qkv, const float* key_bias, void* out, float* lse, int B, int T, int H,
+                                    int DH, float scale, int dtype, passl_stream_t stream);
+
 /* ---------------------------------------------------------------- mixup / cutmix and soft-target cross-entropy
  * Reference: class Mixup, passl_v110/datasets/preprocess/mixup.py:108-276 (the reference mixes on the host, in numpy or
  * through the framework's CPU tensors); SoftTargetCrossEntropy, tasks/ssl/mae/util/loss.py:44-47. */

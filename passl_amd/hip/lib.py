@@ -146,6 +146,10 @@ SIGNATURES = {
     'passl_hip_cait_pos_add': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
     'passl_hip_cait_cls_concat': (c_i, [c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
     'passl_hip_cait_cls_split': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
+    'passl_hip_tome_match': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
+    'passl_hip_tome_merge_fwd': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
+    'passl_hip_tome_merge_bwd': (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
+    'passl_hip_attention_fwd_keybias': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_p]),
     'passl_hip_quick_gelu_fwd': (c_i, [c_p, c_p, c_l, c_i, c_p]),
     'passl_hip_quick_gelu_bwd': (c_i, [c_p, c_p, c_p, c_l, c_i, c_p]),
     'passl_hip_embed_fwd': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),

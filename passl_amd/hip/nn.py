@@ -1456,8 +1456,44 @@ def param_grad_ready(*params):
             a.param_grad_ready(p)
 
 
-def attention(qkv, B, T, H, DH, scale, causal=False):
-    return _AttentionFn.apply(qkv, B, T, H, DH, float(scale), bool(causal))
+def attention(qkv, B, T, H, DH, scale, causal=False, key_bias=None):
+    """``key_bias``: fp32 [B, T] added to every score of its key before the softmax (proportional attention of token
+    merging, log of the token sizes).  Forward only, as the reference uses it (tome.py:279-280)."""
+    if key_bias is None:
+        return _AttentionFn.apply(qkv, B, T, H, DH, float(scale), bool(causal))
+    if causal:
+        raise NotImplementedError('attention(key_bias=...) with the causal mask is not built')
+    if torch.is_grad_enabled() and qkv.requires_grad:
+        raise NotImplementedError('attention(key_bias=...) has no backward: proportional attention is for evaluation '
+                                  '(run it under torch.no_grad())')
+    return ops.attention_fwd_keybias(qkv.contiguous(), key_bias, B, T, H, DH, float(scale))[0]
+
+
+class _ToMeMergeFn(Function):
+    """merge_wavg over a matching: y[row] = sum of size[t] x[t] over the tokens with dest[t] = row, over the sum of
+    their sizes (csrc/tome.hip).  The matching and the sizes carry no gradient; dx is a gather of dy."""
+
+    @staticmethod
+    def forward(ctx, x, size, dest, B, T, r, want_log):
+        _need_contiguous('tome_merge', x=x)
+        res = ops.tome_merge_fwd(x, size, dest, B, T, r, want_log=want_log)
+        ctx.save_for_backward(dest, res[1], *(() if size is None else (size,)))
+        ctx.dims = (B, T, r)
+        ctx.mark_non_differentiable(*res[1:])
+        ctx.set_materialize_grads(False)            # no zero tensor for the sizes' unused gradient (a framework launch)
+        return res
+
+    @staticmethod
+    def backward(ctx, dy, *unused):
+        dest, size_out, *size = ctx.saved_tensors
+        B, T, r = ctx.dims
+        return ops.tome_merge_bwd(dy.contiguous(), size[0] if size else None, size_out, dest, B, T, r), None, None, \
+            None, None, None, None
+
+
+def tome_merge(x, size, dest, B, T, r, want_log=False):
+    """-> (y [B*(T-r), C], size_out fp32 [B, T-r]) and with ``want_log`` also log(size_out)."""
+    return _ToMeMergeFn.apply(x, size, dest, B, T, r, bool(want_log))
 
 
 class _WindowAttentionFn(Function):

@@ -783,6 +783,61 @@ def attention_bwd(qkv, out, dout, lse, B, T, H, DH, scale, causal=False):
     return dqkv
 
 
+# ------------------------------------------------------------------ token merging, ToMe (csrc/tome.hip)
+# the envelope of tome_match (match_shape_ok): the attention kernels', and one A token besides the class token
+TOME_HEAD_DIMS = ATTENTION_HEAD_DIMS
+TOME_MAX_TOKENS = ATTENTION_MAX_TOKENS
+TOME_MIN_TOKENS = 3
+
+
+def tome_max_r(T):
+    """The clamp of tome.py:53 with the class token protected: at most half of the other tokens go."""
+    return (T - 1) // 2
+
+
+def tome_match(qkv, B, T, H, DH, r, want_nodes=False):
+    """qkv [B*T, 3*H*DH] -> dest int32 [B, T], the output row (0 .. T-r-1) of every token (include/passl_hip.h has the
+    order and the tie rule); with ``want_nodes`` also node_max fp32 [B, ceil(T/2)] and node_idx int32."""
+    dest = torch.empty(B, T, dtype=torch.int32, device=qkv.device)
+    nmax = nidx = None
+    if want_nodes:
+        nmax = torch.empty(B, (T + 1) // 2, dtype=torch.float32, device=qkv.device)
+        nidx = torch.empty(B, (T + 1) // 2, dtype=torch.int32, device=qkv.device)
+    L.check(_lib().passl_hip_tome_match(L.ptr(qkv), L.ptr(dest), L.ptr(nmax), L.ptr(nidx), B, T, H, DH, r, L.dt(qkv),
+                                        L.stream()), 'tome_match')
+    return (dest, nmax, nidx) if want_nodes else dest
+
+
+def tome_merge_fwd(x, size, dest, B, T, r, want_log=False):
+    """x [B*T, C], size fp32 [B, T] or None (ones), dest int32 [B, T] -> y [B*(T-r), C], size_out fp32 [B, T-r] and,
+    with ``want_log``, log(size_out)."""
+    Cc = x.shape[-1]
+    y = torch.empty(B * (T - r), Cc, dtype=x.dtype, device=x.device)
+    size_out = torch.empty(B, T - r, dtype=torch.float32, device=x.device)
+    log_out = torch.empty(B, T - r, dtype=torch.float32, device=x.device) if want_log else None
+    L.check(_lib().passl_hip_tome_merge_fwd(L.ptr(x), L.ptr(size), L.ptr(dest), L.ptr(y), L.ptr(size_out),
+                                            L.ptr(log_out), B, T, r, Cc, L.dt(x), L.stream()), 'tome_merge_fwd')
+    return (y, size_out, log_out) if want_log else (y, size_out)
+
+
+def tome_merge_bwd(dy, size, size_out, dest, B, T, r):
+    """dy [B*(T-r), C] -> dx [B*T, C], fully written."""
+    Cc = dy.shape[-1]
+    dx = torch.empty(B * T, Cc, dtype=dy.dtype, device=dy.device)
+    L.check(_lib().passl_hip_tome_merge_bwd(L.ptr(dy), L.ptr(size), L.ptr(size_out), L.ptr(dest), L.ptr(dx), B, T, r,
+                                            Cc, L.dt(dy), L.stream()), 'tome_merge_bwd')
+    return dx
+
+
+def attention_fwd_keybias(qkv, key_bias, B, T, H, DH, scale):
+    """attention_fwd with score + key_bias[b, j] before the softmax; key_bias fp32 [B, T].  Forward only."""
+    out = torch.empty(B * T, H * DH, dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty(B, H, T, dtype=torch.float32, device=qkv.device)
+    L.check(_lib().passl_hip_attention_fwd_keybias(L.ptr(qkv), L.ptr(key_bias), L.ptr(out), L.ptr(lse), B, T, H, DH,
+                                                   scale, L.dt(qkv), L.stream()), 'attention_fwd_keybias')
+    return out, lse
+
+
 # ------------------------------------------------------------------ Swin Transformer (csrc/window_attention.hip)
 WINDOW_ATTENTION_MAX_WINDOW = 14
 WINDOW_ATTENTION_WORKGROUPS = 2048   # include/passl_hip.h: PASSL_WINDOW_ATTENTION_WORKGROUPS

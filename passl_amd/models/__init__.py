@@ -102,9 +102,18 @@ from .simsiam import (SimSiamPretain, SimSiamLinearProbe, simsiam_resnet50_pretr
 def build_model(config):
     config = copy.deepcopy(dict(config))
     model_type = config.pop('name')
+    tome_cfg = config.pop('tome', None)         # {r, prop_attn}: token merging, applied to the constructed model
     factory = getattr(sys.modules[__name__], model_type, None)
     if factory is None or not callable(factory):
         raise AttributeError('passl.models has no model named %r' % (model_type,))
     model = factory(**config)
     assert isinstance(model, Model), 'model must inherit from passl.models.Model'
+    if tome_cfg is not None:
+        from .utils import tome
+        tome_cfg = dict(tome_cfg)
+        r = tome_cfg.pop('r', 0)
+        tome.apply_patch(model, prop_attn=bool(tome_cfg.pop('prop_attn', False)))
+        if tome_cfg:
+            raise ValueError('Model.tome: unknown keys %s (known: r, prop_attn)' % sorted(tome_cfg))
+        model.r = tuple(r) if isinstance(r, (list, tuple)) and len(r) == 2 and isinstance(r[1], float) else r
     return model

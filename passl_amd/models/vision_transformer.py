@@ -127,6 +127,7 @@ class VisionTransformer(ViTTrunk, Model):
         return self.cls_features(self.run_blocks(x, B, L + 1), cls_rows, self.norm)
 
     def forward(self, x):
+        self.arena_q.refresh()                       # compute-dtype operands and data-gradient packs of the updated weights
         x = self.forward_features(x)
         if self.representation_size is not None:
             x = self.tanh(self.head0(x))
