@@ -906,6 +906,39 @@ int passl_hip_tome_merge_bwd(const void* dy, const float* size, const float* siz
  * options; with key_bias = 0 the output has the bits of passl_hip_attention_fwd. */
 int passl_hip_attention_fwd_keybias(const void* qkv, const float* key_bias, void* out, float* lse, int B, int T, int H,
                                     int DH, float scale, int dtype, passl_stream_t stream);
+/* Key-tiled attention for longer sequences (csrc/attention_tiled.hip): the layouts and the result of
+ * passl_hip_attention_fwd / _bwd without a causal flag — qkv [B,T,3,H,DH], out and dout [B,T,H,DH], lse fp32 [B,H,T],
+ * dqkv [B,T,3,H,DH] fully written.  Replaces Attention.forward, passl/models/vision_transformer.py:142-156, at the 577 /
+ * 578 tokens of DeiT at 384 pixels (passl/models/deit.py).
+ * A workgroup owns a block of query rows of one (image, head) — the grid is over (image, head, block) — and streams the
+ * head's K and V through LDS 64 rows at a time under an online softmax in fp32 (running max, running sum, an accumulator
+ * rescaled when the max rises; out = accumulator / sum at the end): the T x T scores never reach memory and the LDS
+ * footprint does not depend on T.  The backward is two sweeps, own query rows against streamed K and V blocks for dQ and
+ * own key columns against streamed Q and dO blocks for dK and dV; P is recomputed from lse, delta_i = dO_i . O_i.  No
+ * atomics, no scratch, no workspace: two launches give the same bits.
+ * Operands as in passl_hip_attention_fwd: fp32 activations, and bf16 activations of which some pointer is not 16-byte
+ * aligned, use exact-fp32 MFMA; aligned bf16 activations use bf16 MFMA and round P (unnormalised, exp(s - running max))
+ * or dS as the operand of the second product, and every store.
+ * Accepted: 1 <= T <= 1024, DH in {32, 64}, B and H positive (PASSL_EUNSUPPORTED otherwise, and for an unknown dtype);
+ * a NULL pointer is PASSL_EINVAL.  Nothing is launched unless PASSL_OK is returned. */
+int passl_hip_attention_tiled_fwd(const void* qkv, void* out, float* lse, int B, int T, int H, int DH, float scale,
+                                  int dtype, passl_stream_t stream);
+int passl_hip_attention_tiled_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv,
+                                  int B, int T, int H, int DH, float scale, int dtype, passl_stream_t stream);
+/* Token assembly with NP = 1 or 2 learnable prefix rows (csrc/deit_tokens.hip; DistilledVisionTransformer.forward_features,
+ * passl/models/deit.py:238-247: concat(cls_token, dist_token, patches) + pos_embed).  x [B, L, C] and out [B, NP + L, C] in
+ * `dtype`; prefix0, prefix1 fp32 [C] (prefix1 is not read when NP = 1 and may be NULL), pos fp32 [NP + L, C]:
+ *   out[b, t] = (t < NP ? prefix_t : x[b, t - NP]) + pos[t].
+ * The backward writes dx[b, t - NP] = dout[b, NP + t] fully and ADDS sum_b dout[b, t] to dprefix_t (fp32 [C], images in
+ * order); dpos is passl_hip_colsum_acc over dout as [B, (NP + L) C].  One streaming launch each; no atomics, two runs give
+ * the same bits.  C % 8 == 0, every pointer 16-byte aligned, NP in {1, 2} (PASSL_EINVAL otherwise). */
+int passl_hip_prefix_tokens_fwd(const void* x, const float* prefix0, const float* prefix1, const float* pos, void* out,
+                                int B, int L, int NP, int C, int dtype, passl_stream_t stream);
+int passl_hip_prefix_tokens_bwd(const void* dout, void* dx, float* dprefix0, float* dprefix1, int B, int L, int NP, int C,
+                                int dtype, passl_stream_t stream);
+/* out[i] = (a[i] + b[i]) / 2 over n fp32 elements: the distilled DeiT's (head(x) + head_dist(x_dist)) / 2 (deit.py:259).
+ * b == NULL: out = a / 2, the gradient both heads receive.  n > 0 and a, out non-NULL (PASSL_EINVAL otherwise). */
+int passl_hip_mean2(const float* a, const float* b, float* out, int64_t n, passl_stream_t stream);
 
 /* ---------------------------------------------------------------- mixup / cutmix and soft-target cross-entropy
  * Reference: class Mixup, passl_v110/datasets/preprocess/mixup.py:108-276 (the reference mixes on the host, in numpy or

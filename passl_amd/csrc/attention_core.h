@@ -16,8 +16,8 @@
 // recomputed from the saved row log-sum-exp by Ops::prob; delta_i = dO_i . O_i).
 // `causal` (CLIP text tower, passl_v110/modeling/backbones/clip.py:284-286: additive triu(-inf, 1)
 // mask): key j is visible to query i iff j <= i; fully masked tiles are skipped.
-// Limits: d in {32, 64}, T <= 208 (13 tiles) — the MAE pre-training shapes; larger T needs a
-// KV-tiled (flash-style) variant.
+// Limits: d in {32, 64}, T <= 208 (13 tiles) — the MAE pre-training shapes; larger T takes the
+// KV-tiled (flash-style) variant of attention_tiled.hip.
 //
 // Ops supplies
 //   elem_t, lds_t        element type in memory and in LDS

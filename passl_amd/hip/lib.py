@@ -133,6 +133,8 @@ SIGNATURES = {
     'passl_hip_tanh_bwd': (c_i, [c_p, c_p, c_p, c_l, c_i, c_p]),
     'passl_hip_attention_fwd': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_p]),
     'passl_hip_attention_bwd': (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_p]),
+    'passl_hip_attention_tiled_fwd': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_p]),
+    'passl_hip_attention_tiled_bwd': (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_p]),
     'passl_hip_window_attention_fwd': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_p]),
     'passl_hip_window_attention_bwd': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
                                              c_f, c_i, c_p]),
@@ -146,6 +148,9 @@ SIGNATURES = {
     'passl_hip_cait_pos_add': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
     'passl_hip_cait_cls_concat': (c_i, [c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
     'passl_hip_cait_cls_split': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
+    'passl_hip_prefix_tokens_fwd': (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
+    'passl_hip_prefix_tokens_bwd': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
+    'passl_hip_mean2': (c_i, [c_p, c_p, c_p, c_l, c_p]),
     'passl_hip_tome_match': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
     'passl_hip_tome_merge_fwd': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
     'passl_hip_tome_merge_bwd': (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),

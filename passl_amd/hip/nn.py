@@ -1436,6 +1436,24 @@ class _AttentionFn(Function):
             None, None, None, None
 
 
+class _AttentionTiledFn(Function):
+    """_AttentionFn beyond ops.ATTENTION_MAX_TOKENS: the key-tiled kernels (csrc/attention_tiled.hip), no causal flag."""
+
+    @staticmethod
+    def forward(ctx, qkv, B, T, H, DH, scale):
+        out, lse = ops.attention_tiled_fwd(qkv.contiguous(), B, T, H, DH, scale)
+        ctx.save_for_backward(qkv, out, lse)
+        ctx.dims = (B, T, H, DH, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse = ctx.saved_tensors
+        B, T, H, DH, scale = ctx.dims
+        return ops.attention_tiled_bwd(qkv, out, dout.contiguous(), lse, B, T, H, DH, scale), None, None, None, None, \
+            None
+
+
 def param_expect_grad(*params):
     """Called from the FORWARD of a custom Function that will report ``param_grad_ready`` for these raw arena parameters
     from its backward: a parameter used by several forward nodes of one step (a trunk run once per view) is complete —
@@ -1458,7 +1476,13 @@ def param_grad_ready(*params):
 
 def attention(qkv, B, T, H, DH, scale, causal=False, key_bias=None):
     """``key_bias``: fp32 [B, T] added to every score of its key before the softmax (proportional attention of token
-    merging, log of the token sizes).  Forward only, as the reference uses it (tome.py:279-280)."""
+    merging, log of the token sizes).  Forward only, as the reference uses it (tome.py:279-280).
+    Beyond ``ops.ATTENTION_MAX_TOKENS`` tokens the key-tiled kernels take over; they have neither mask nor bias."""
+    if T > ops.ATTENTION_MAX_TOKENS:
+        if causal or key_bias is not None:
+            raise NotImplementedError('attention(causal / key_bias) beyond %d tokens is not built: the key-tiled '
+                                      'kernels have neither' % ops.ATTENTION_MAX_TOKENS)
+        return _AttentionTiledFn.apply(qkv, B, T, H, DH, float(scale))
     if key_bias is None:
         return _AttentionFn.apply(qkv, B, T, H, DH, float(scale), bool(causal))
     if causal:
@@ -1467,6 +1491,55 @@ def attention(qkv, B, T, H, DH, scale, causal=False, key_bias=None):
         raise NotImplementedError('attention(key_bias=...) has no backward: proportional attention is for evaluation '
                                   '(run it under torch.no_grad())')
     return ops.attention_fwd_keybias(qkv.contiguous(), key_bias, B, T, H, DH, float(scale))[0]
+
+
+class _PrefixTokensFn(Function):
+    """rows[b] = [prefix rows | x[b]] + pos with one or two learnable prefix rows and a learnable position table
+    (csrc/deit_tokens.hip).  Backward: dx is a copy, each dprefix the batch sum of its row of dout, dpos the column sum."""
+
+    @staticmethod
+    def forward(ctx, x, pos, B, L, *prefixes):
+        ctx.params = tuple(prefixes) + (pos,)
+        ctx.dims = (B, L)
+        param_expect_grad(*ctx.params)
+        return ops.prefix_tokens_fwd(x.contiguous(), [p.detach().view(-1) for p in prefixes],
+                                     pos.detach().view(-1, pos.shape[-1]), B, L)
+
+    @staticmethod
+    def backward(ctx, dout):
+        B, L = ctx.dims
+        for p in ctx.params:
+            if p.grad is None:
+                p.grad = torch.zeros_like(p)
+        dout = dout.contiguous()
+        dx = ops.prefix_tokens_bwd(dout, [p.grad.view(-1) for p in ctx.params[:-1]], B, L)
+        ops.colsum_into(dout.view(B, -1), ctx.params[-1].grad.view(-1), accumulate=True)    # dpos[t] += sum_b dout[b, t]
+        param_grad_ready(*ctx.params)
+        return (dx, None, None, None) + (None,) * (len(ctx.params) - 1)
+
+
+def prefix_tokens(x, prefixes, pos, B, L):
+    """x [B*L, C] -> [B*(len(prefixes) + L), C]: concat(*prefixes, x) + pos (deit.py:242-246)."""
+    return _PrefixTokensFn.apply(x, pos, B, L, *prefixes)
+
+
+class _Mean2Fn(Function):
+    """(a + b) / 2 on fp32 logits in one launch; both inputs receive dy / 2."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        return ops.mean2(a.contiguous(), b.contiguous())
+
+    @staticmethod
+    def backward(ctx, dy):
+        g = ops.mean2(dy.contiguous())
+        return g, g
+
+
+def mean2(a, b):
+    if a.dtype != torch.float32 or b.dtype != torch.float32 or a.shape != b.shape:
+        raise ValueError('mean2 takes two fp32 tensors of one shape')
+    return _Mean2Fn.apply(a, b)
 
 
 class _ToMeMergeFn(Function):
@@ -1733,6 +1806,31 @@ class _GatherRowsFn(Function):
 
 def gather_rows(x, idx):
     return _GatherRowsFn.apply(x, idx)
+
+
+class _SplitRowsFn(Function):
+    """x [M, C] -> (x[:n], x[n:]) as tensors of their own (two library copies); the backward writes both gradients
+    into one [M, C] buffer.  A slice's own backward would be ATen launches inside the step."""
+
+    @staticmethod
+    def forward(ctx, x, n):
+        x = x.contiguous()
+        ctx.n, ctx.shape = n, x.shape
+        return ops.clone(x[:n]), ops.clone(x[n:])
+
+    @staticmethod
+    def backward(ctx, d0, d1):
+        dx = torch.empty(ctx.shape, dtype=(d0 if d0 is not None else d1).dtype, device=(d0 if d0 is not None else d1).device)
+        for part, d in ((dx[:ctx.n], d0), (dx[ctx.n:], d1)):
+            if d is None:
+                ops.fill_zero(part)
+            else:
+                ops.copy_into(part, d.contiguous())
+        return dx, None
+
+
+def split_rows(x, n):
+    return _SplitRowsFn.apply(x, n)
 
 
 # =============================================================================== head pieces

@@ -783,6 +783,54 @@ def attention_bwd(qkv, out, dout, lse, B, T, H, DH, scale, causal=False):
     return dqkv
 
 
+# the envelope of csrc/attention_tiled.hip (check_shape): the key-tiled kernels, same head dimensions, no causal flag
+ATTENTION_TILED_MAX_TOKENS = 1024
+
+
+def attention_tiled_fwd(qkv, B, T, H, DH, scale):
+    """qkv [B*T, 3*H*DH] -> out [B*T, H*DH], lse [B, H, T]; T <= ATTENTION_TILED_MAX_TOKENS."""
+    out = torch.empty(B * T, H * DH, dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty(B, H, T, dtype=torch.float32, device=qkv.device)
+    L.check(_lib().passl_hip_attention_tiled_fwd(L.ptr(qkv), L.ptr(out), L.ptr(lse), B, T, H, DH, scale, L.dt(qkv),
+                                                 L.stream()), 'attention_tiled_fwd')
+    return out, lse
+
+
+def attention_tiled_bwd(qkv, out, dout, lse, B, T, H, DH, scale):
+    dqkv = torch.empty_like(qkv)
+    L.check(_lib().passl_hip_attention_tiled_bwd(L.ptr(qkv), L.ptr(out), L.ptr(dout), L.ptr(lse), L.ptr(dqkv), B, T, H,
+                                                 DH, scale, L.dt(qkv), L.stream()), 'attention_tiled_bwd')
+    return dqkv
+
+
+# ------------------------------------------------------------------ DeiT token assembly (csrc/deit_tokens.hip)
+def prefix_tokens_fwd(x, prefixes, pos, B, Ln):
+    """x [B*L, C], prefixes: one or two fp32 [C] rows, pos fp32 [NP + L, C] -> [B*(NP + L), C] = [prefixes | x] + pos."""
+    NP, D = len(prefixes), x.shape[-1]
+    out = torch.empty(B * (NP + Ln), D, dtype=x.dtype, device=x.device)
+    p1 = prefixes[1] if NP > 1 else None
+    L.check(_lib().passl_hip_prefix_tokens_fwd(L.ptr(x), L.ptr(prefixes[0]), L.ptr(p1), L.ptr(pos), L.ptr(out), B, Ln, NP,
+                                               D, L.dt(x), L.stream()), 'prefix_tokens_fwd')
+    return out
+
+
+def prefix_tokens_bwd(dout, dprefixes, B, Ln):
+    """dout [B*(NP + L), C] -> dx [B*L, C]; dprefixes[t] (fp32 [C]) += sum_b dout[b, t]."""
+    NP, D = len(dprefixes), dout.shape[-1]
+    dx = torch.empty(B * Ln, D, dtype=dout.dtype, device=dout.device)
+    d1 = dprefixes[1] if NP > 1 else None
+    L.check(_lib().passl_hip_prefix_tokens_bwd(L.ptr(dout), L.ptr(dx), L.ptr(dprefixes[0]), L.ptr(d1), B, Ln, NP, D,
+                                               L.dt(dout), L.stream()), 'prefix_tokens_bwd')
+    return dx
+
+
+def mean2(a, b=None):
+    """(a + b) / 2 over fp32 tensors of one shape; ``b`` None: a / 2."""
+    out = torch.empty_like(a)
+    L.check(_lib().passl_hip_mean2(L.ptr(a), L.ptr(b), L.ptr(out), a.numel(), L.stream()), 'mean2')
+    return out
+
+
 # ------------------------------------------------------------------ token merging, ToMe (csrc/tome.hip)
 # the envelope of tome_match (match_shape_ok): the attention kernels', and one A token besides the class token
 TOME_HEAD_DIMS = ATTENTION_HEAD_DIMS

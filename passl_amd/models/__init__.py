@@ -92,6 +92,8 @@ from .swin_transformer import *                                       # noqa: E4
 from .swin_transformer import SwinTransformer                         # noqa: E402,F401
 from .cait import *                                                   # noqa: E402,F401,F403  (passl/models/__init__.py:28)
 from .cait import Cait                                                # noqa: E402,F401
+from .deit import *                                                   # noqa: E402,F401,F403  (passl/models/__init__.py:29)
+from .deit import DeitVisionTransformer, DistilledVisionTransformer   # noqa: E402,F401
 from .mae import *                                                    # noqa: E402,F401,F403  (passl/models/__init__.py:31)
 from .mae import (MaskedAutoencoderViT, mae_vit_base_patch16_dec512d8b, mae_vit_large_patch16_dec512d8b,   # noqa: E402,F401
                   mae_vit_huge_patch14_dec512d8b)

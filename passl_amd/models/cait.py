@@ -27,7 +27,7 @@ Evaluation mode and rate 0 launch no draw.
 Envelope: the kernels take head dimension 48 (every factory's), at most 8 heads and 208 tokens.  The three 224-pixel
 factories (``cait_xxs24_224``, ``cait_xxs36_224``, ``cait_s24_224``) run.  The seven 384- / 448-pixel factories (576 /
 784 patch tokens, 16 heads for the m sizes) construct with the reference's keys and raise the library's unsupported
-error (PASSL_EUNSUPPORTED) when run, as the large v2 ViT factories do: they need a key-tiled kernel that is not built.
+error (PASSL_EUNSUPPORTED) when run, as the large v2 ViT factories do: they need a key-tiled talking-heads kernel that is not built.
 
 Initialisation (:324-335): trunc-normal(0.02) Linear weights (proj_l / proj_w included), ``pos_embed`` and ``cls_token``,
 zero biases, LayerNorm (1, 0), gamma = ``init_values``; the patch convolution keeps Paddle's default.
