@@ -791,6 +791,84 @@ int passl_hip_layer_scale_add_bwd(const void* dy, const void* branch, const floa
                                   float keep_prob, void* dbranch, float* dgamma, float* ws, int64_t ws_floats, int B,
                                   int T, int C, int dtype, passl_stream_t stream);
 
+/* ---------------------------------------------------------------- ConvMAE (csrc/convmae.hip)
+ * Reference: class CBlock, passl/models/convmae/conv_vit.py:82-99: `self.attn = nn.Conv2D(dim, dim, 5, padding=2,
+ * groups=dim)` applied to `mask * conv1(norm1(x))`.  x, y, dy, dx are NHWC [N][H][W][C] in `dtype`; w is fp32 in the
+ * parameter's own layout [C][1][5][5] (25 * C floats, read as it lies), bias fp32 [C].  C % 8 == 0, every tensor 16-byte
+ * aligned, any H, W >= 1.  fp32 accumulation, one rounding to `dtype` at the store; no floating-point atomics: every
+ * result is bit-reproducible from launch to launch.
+ * mask: the fp32 table [N][Hm * Wm] of passl_hip_mae_mask (1 = removed), or NULL for no mask (Hm, Wm are then not
+ * read).  With g = H / Hm = W / Wm (an integer >= 1), keep(n, h, w) = 1 - mask[n][(h / g) * Wm + w / g]; no map-sized
+ * mask tensor exists.  A factor of exactly 0 or 1 is applied exactly (a removed pixel is not even loaded); any other
+ * factor is applied in fp32 and, for a bf16 input, rounded to bf16 once when the pixel is staged.
+ * NULL pointers (but `mask`), sizes <= 0, C % 8, misalignment, a short workspace, H % Hm, W % Wm, H / Hm != W / Wm ->
+ * PASSL_EINVAL; an unknown dtype or a grid beyond 2^31 workgroups -> PASSL_EUNSUPPORTED. */
+
+/* y[n,h,w,c] = bias[c] + sum_{r,s} w[c,0,r,s] * keep(n,h+r-2,w+s-2) * x[n,h+r-2,w+s-2,c], zero padding. */
+int passl_hip_dwconv5_masked_fwd(const void* x, const float* w, const float* bias, const float* mask, void* y, int N,
+                                 int H, int W, int C, int Hm, int Wm, int dtype, passl_stream_t stream);
+/* dx[n,h,w,c] = keep(n,h,w) * sum_{r,s} dy[n,h+2-r,w+2-s,c] * w[c,0,r,s]; a removed pixel gets +0. */
+int passl_hip_dwconv5_masked_bwd_data(const void* dy, const float* w, const float* mask, void* dx, int N, int H, int W,
+                                      int C, int Hm, int Wm, int dtype, passl_stream_t stream);
+/* dw[c,0,r,s] = sum_{n,p,q} dy[n,p,q,c] * keep(n,p+r-2,q+s-2) * x[n,p+r-2,q+s-2,c] and dbias[c] = sum dy, WRITTEN (not
+ * accumulated) in fp32.  Every workgroup leaves its sums in a slab of ws and a second and third launch add the slabs in
+ * ascending order.  ws_floats >= PASSL_DWCONV5_WGRAD_WS_FLOATS(N, H, W, C). */
+#define PASSL_DWCONV5_WGRAD_TILE_H 8
+#define PASSL_DWCONV5_WGRAD_TILE_W 16
+#define PASSL_DWCONV5_WGRAD_MAX_SLABS 512
+#define PASSL_DWCONV5_WGRAD_TILES(N, H, W)                                                  \
+  ((int64_t)(N) * (((H) + PASSL_DWCONV5_WGRAD_TILE_H - 1) / PASSL_DWCONV5_WGRAD_TILE_H) *   \
+   (((W) + PASSL_DWCONV5_WGRAD_TILE_W - 1) / PASSL_DWCONV5_WGRAD_TILE_W))
+#define PASSL_DWCONV5_WGRAD_SLABS(N, H, W)                                        \
+  (PASSL_DWCONV5_WGRAD_TILES(N, H, W) < PASSL_DWCONV5_WGRAD_MAX_SLABS             \
+       ? PASSL_DWCONV5_WGRAD_TILES(N, H, W) : (int64_t)PASSL_DWCONV5_WGRAD_MAX_SLABS)
+#define PASSL_DWCONV5_WGRAD_WS_FLOATS(N, H, W, C) (PASSL_DWCONV5_WGRAD_SLABS(N, H, W) * 26 * (C))
+int passl_hip_dwconv5_masked_bwd_weight(const void* x, const void* dy, const float* mask, float* dw, float* dbias,
+                                        float* ws, int64_t ws_floats, int N, int H, int W, int C, int Hm, int Wm,
+                                        int dtype, passl_stream_t stream);
+
+/* The kept patches of an NHWC map as GEMM rows (conv_mae.py:249-266 runs the stage decoders and patch_embed3 over all
+ * patches and then keeps K of them; they are per-patch functions, so they run on the kept ones only).
+ * x [B][Hm*p][Wm*p][C], ids_keep int32 [B][K] (patch numbers of the Hm x Wm grid, as passl_hip_mae_mask writes them),
+ * out [B*K][p*p*C] with column order (ph, pw, c): the K-order of a patch convolution's weight stored [Cout][p][p][C].
+ * An index outside the grid gives a row of zeros.  C % 8 == 0, K <= Hm * Wm. */
+int passl_hip_patch_gather_fwd(const void* x, const int32_t* ids_keep, void* out, int B, int K, int Hm, int Wm, int p,
+                               int C, int dtype, passl_stream_t stream);
+/* Its backward: dx [B][Hm*p][Wm*p][C] fully written from dout [B*K][p*p*C] and ids_restore int32 [B][Hm*Wm] (the rank
+ * of every patch): zeros at the patches whose rank is >= K.  A pixel belongs to exactly one patch: no atomics. */
+int passl_hip_patch_gather_bwd(const void* dout, const int32_t* ids_restore, void* dx, int B, int K, int Hm, int Wm,
+                               int p, int C, int dtype, passl_stream_t stream);
+
+/* MAE token kernels for a model WITHOUT a class row (conv_mae.py); x, out, dout, dx in `dtype`, pos and mask_token
+ * fp32, D % 8 == 0, 1 <= K <= L.
+ * encoder input: out[b,k] = x[b,k] + pos[ids_keep[b,k]];  x, out [B][K][D], pos [L][D].  Its data gradient is dout. */
+int passl_hip_tokens_pos_gather_add(const void* x, const float* pos, const int32_t* ids_keep, void* out, int B, int L,
+                                    int K, int D, int dtype, passl_stream_t stream);
+/* dpos [L][D] fp32, ACCUMULATED as the other parameter gradients of the token kernels are: dpos[l] += the sum over the
+ * images b = 0, 1, ... (added in that order, from 0) whose rank r = ids_restore[b,l] is < K of dout[b,r]. */
+int passl_hip_tokens_pos_gather_add_bwd(const void* dout, const int32_t* ids_restore, float* dpos, int B, int L, int K,
+                                        int D, int dtype, passl_stream_t stream);
+/* decoder input: out[b,l] = ((r = ids_restore[b,l]) < K ? x[b,r] : mask_token) + pos[l];  x [B][K][D], out [B][L][D]. */
+int passl_hip_tokens_unshuffle(const void* x, const float* mask_token, const float* pos, const int32_t* ids_restore,
+                               void* out, int B, int L, int K, int D, int dtype, passl_stream_t stream);
+/* its backward: dx [B][K][D] fully written (dx[b,k] = dout[b,ids_keep[b,k]]), dmask_token += sum of dout over the
+ * removed positions (position-block slabs in `ws`, added in order: no atomics).
+ * ws_floats >= PASSL_TOKENS_UNSHUFFLE_BWD_WS_FLOATS(D) covers every shape. */
+#define PASSL_TOKENS_UNSHUFFLE_MAX_SLABS 1024
+#define PASSL_TOKENS_UNSHUFFLE_BWD_WS_FLOATS(D) ((int64_t)PASSL_TOKENS_UNSHUFFLE_MAX_SLABS * (D))
+int passl_hip_tokens_unshuffle_bwd(const void* dout, const int32_t* ids_keep, const int32_t* ids_restore, void* dx,
+                                   float* dmask_token, int B, int L, int K, int D, int dtype, float* ws,
+                                   int64_t ws_floats, passl_stream_t stream);
+
+/* forward_loss (conv_mae.py:300-316) on pred fp32 [B][L][P] with no class row: passl_hip_mae_loss_fwd / _bwd
+ * otherwise.  ws: B * L floats (the per-patch terms, summed in one fixed order). */
+int passl_hip_tokens_mae_loss_fwd(const float* img, const float* pred, const float* mask, float* loss, int B, int C,
+                                  int H, int W, int p, int norm_pix, float denom, float* ws, int64_t ws_floats,
+                                  passl_stream_t stream);
+int passl_hip_tokens_mae_loss_bwd(const float* img, const float* pred, const float* mask, const float* gscale,
+                                  float* dpred, int B, int C, int H, int W, int p, int norm_pix, float denom,
+                                  passl_stream_t stream);
+
 /* ---------------------------------------------------------------- Swin Transformer (csrc/window_attention.hip)
  * Reference: WindowAttention.forward, passl/models/swin_transformer.py:112-200, with the roll, window_partition,
  * attn_mask, window_reverse and roll of SwinTransformerBlock.forward :291-340 as address arithmetic.

@@ -187,6 +187,18 @@ SIGNATURES = {
     'passl_hip_dwconv7_fwd': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
     'passl_hip_dwconv7_bwd_data': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
     'passl_hip_dwconv7_bwd_weight': (c_i, [c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_i, c_p]),
+    'passl_hip_dwconv5_masked_fwd': (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
+    'passl_hip_dwconv5_masked_bwd_data': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
+    'passl_hip_dwconv5_masked_bwd_weight': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
+                                                  c_p]),
+    'passl_hip_patch_gather_fwd': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
+    'passl_hip_patch_gather_bwd': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
+    'passl_hip_tokens_pos_gather_add': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
+    'passl_hip_tokens_pos_gather_add_bwd': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
+    'passl_hip_tokens_unshuffle': (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
+    'passl_hip_tokens_mae_loss_fwd': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_l, c_p]),
+    'passl_hip_tokens_mae_loss_bwd': (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p]),
+    'passl_hip_tokens_unshuffle_bwd': (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_l, c_p]),
     'passl_hip_layer_scale_add_fwd': (c_i, [c_p, c_p, c_p, c_p, c_f, c_p, c_i, c_i, c_i, c_i, c_p]),
     'passl_hip_layer_scale_add_bwd': (c_i, [c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_p]),
     'passl_hip_batch_mix': (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_p]),

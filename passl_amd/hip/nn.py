@@ -1009,6 +1009,183 @@ class DepthwiseConv2D(Layer):
         return _DepthwiseConvFn.apply(x, self.weight, self.bias, self, add_slot)
 
 
+# =============================================================================== ConvMAE pieces (csrc/convmae.hip)
+class _MaskedDepthwiseConvFn(Function):
+    """Depthwise 5x5 over NHWC of `keep * x`, keep = 1 - mask expanded from the patch grid by address arithmetic (no
+    map-sized mask tensor).  No add_slot: a CBlock's residual forks before norm1, not at the convolution.  dW and dbias
+    are WRITTEN straight into the parameters' gradients, on the side stream when there is one."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, layer, mask, grid):
+        _need_contiguous('MaskedDepthwiseConv2D', x=x)
+        y = ops.dwconv5_masked_fwd(x, weight.detach(), bias.detach(), mask, grid)
+        if layer._rt is not None and any(ctx.needs_input_grad):
+            layer._rt.arena.expect_grad(layer._rt.indices)
+        ctx.save_for_backward(x)
+        ctx.layer, ctx.mask, ctx.grid = layer, mask, grid
+        ctx.side = streams.enabled(x)              # latched for the backward (see _ConvFn)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        layer, mask, grid = ctx.layer, ctx.mask, ctx.grid
+        dy = dy.contiguous()
+        for p in (layer.weight, layer.bias):
+            if p.grad is None:
+                p.grad = ops.zeros(*p.shape, dtype=p.dtype, device=p.device)      # (outside an arena; a library fill)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = ops.dwconv5_masked_bwd_data(dy, layer.weight.detach(), mask, grid)
+        dw, db = layer.weight.grad, layer.bias.grad
+        reads = (x, dy) if mask is None else (x, dy, mask)
+        if ctx.side:
+            streams.side_later(dy.device, lambda: ops.dwconv5_masked_bwd_weight_into(x, dy, dw, db, mask, grid),
+                               reads=reads)
+        else:
+            ops.dwconv5_masked_bwd_weight_into(x, dy, dw, db, mask, grid)
+        if layer._rt is not None:
+            layer._rt.arena.grad_ready(layer._rt.indices)
+        return dx, None, None, None, None, None
+
+
+class MaskedDepthwiseConv2D(Layer):
+    """paddle.nn.Conv2D(dim, dim, kernel_size=5, padding=2, groups=dim) over NHWC activations, applied to ``mask * x``
+    as a ConvMAE CBlock does (conv_vit.py:82-99): parameters ``weight [dim, 1, 5, 5]`` and ``bias [dim]`` in the
+    reference's layout, read by the kernels as they lie."""
+
+    def __init__(self, dim, kernel_size=5, padding=2):
+        super().__init__()
+        if kernel_size != 5:
+            raise NotImplementedError('MaskedDepthwiseConv2D: kernel_size %r (the HIP kernels are 5x5)' % (kernel_size,))
+        if padding != 2:
+            raise NotImplementedError('MaskedDepthwiseConv2D: padding %r (the HIP kernels pad by 2)' % (padding,))
+        if dim <= 0 or dim % 8:
+            raise NotImplementedError('MaskedDepthwiseConv2D: dim %r is not a positive multiple of 8' % (dim,))
+        dev = config.get_device()
+        self.dim = dim
+        self.weight = tnn.Parameter(torch.empty(dim, 1, 5, 5, device=dev))
+        self.bias = tnn.Parameter(torch.zeros(dim, device=dev))
+        self._rt = None
+
+    def forward(self, x, mask=None, grid=None):
+        """x: [N, H, W, dim] in the compute dtype.  mask: the fp32 table [N, Hm * Wm] of ops.mae_mask (1 = removed) with
+        grid = (Hm, Wm), H / Hm == W / Wm an integer; None: no mask (the ConvViT path)."""
+        if mask is not None:
+            if grid is None:
+                raise ValueError('MaskedDepthwiseConv2D: a mask needs its grid (Hm, Wm)')
+            Hm, Wm = grid
+            H, W = x.shape[1], x.shape[2]
+            if Hm <= 0 or Wm <= 0 or H % Hm or W % Wm or H // Hm != W // Wm:
+                raise ValueError('MaskedDepthwiseConv2D: a %d x %d map does not lie over a %d x %d mask grid by one '
+                                 'integer factor' % (H, W, Hm, Wm))
+            _need_contiguous('MaskedDepthwiseConv2D', mask=mask)
+        return _MaskedDepthwiseConvFn.apply(x, self.weight, self.bias, self, mask, None if mask is None else tuple(grid))
+
+
+class _PatchGatherFn(Function):
+    """The kept patches of an NHWC map as GEMM rows [B*K, p*p*C]; the backward writes every pixel of dx."""
+
+    @staticmethod
+    def forward(ctx, x, ids_keep, ids_restore, grid, p):
+        _need_contiguous('patch_gather', x=x)
+        ctx.ids_restore, ctx.grid, ctx.p = ids_restore, grid, p
+        ctx.B, ctx.K, ctx.C = x.shape[0], ids_keep.shape[1], x.shape[3]
+        return ops.patch_gather_fwd(x, ids_keep, grid, p)
+
+    @staticmethod
+    def backward(ctx, dout):
+        dx = ops.patch_gather_bwd(dout.contiguous(), ctx.ids_restore, ctx.B, ctx.K, ctx.grid, ctx.p, ctx.C)
+        return dx, None, None, None, None
+
+
+def patch_gather(x, ids_keep, ids_restore, grid, p):
+    """x [B, Hm*p, Wm*p, C] -> rows [B*K, p*p*C] of the patches ids_keep [B, K] names, column order (ph, pw, c): the
+    operand of a patch convolution's GEMM restricted to the kept patches."""
+    return _PatchGatherFn.apply(x, ids_keep, ids_restore, tuple(grid), p)
+
+
+class _TokensPosGatherAddFn(Function):
+    """out[b, k] = x[b, k] + pos[ids_keep[b, k]] (no class row).  dx is dout; a learnable ``pos`` (conv_mae.py leaves
+    ``pos_embed`` trainable) gets its gradient added into ``pos.grad``, the images in ascending order."""
+
+    @staticmethod
+    def forward(ctx, x, pos, ids_keep, ids_restore, B, L):
+        learnable = isinstance(pos, tnn.Parameter) and pos.requires_grad
+        ctx.ids_restore, ctx.dims = ids_restore, (B, L, ids_keep.shape[1])
+        ctx.params = (pos,) if learnable else ()
+        param_expect_grad(*ctx.params)
+        return ops.tokens_pos_gather_add(x, pos.detach().view(-1, pos.shape[-1]), ids_keep, B, L, ids_keep.shape[1])
+
+    @staticmethod
+    def backward(ctx, dout):
+        B, L, K = ctx.dims
+        dout = dout.contiguous()
+        for pos in ctx.params:
+            if pos.grad is None:
+                pos.grad = torch.zeros_like(pos)
+            ops.tokens_pos_gather_add_bwd_into(dout, ctx.ids_restore, pos.grad.view(-1, pos.shape[-1]), B, L, K)
+        param_grad_ready(*ctx.params)
+        return dout, None, None, None, None, None
+
+
+def tokens_pos_gather_add(x, pos, ids_keep, ids_restore, B, L):
+    """x [B*K, D] + the rows of pos [1, L, D] (a buffer or a learnable table) that ids_keep [B, K] names."""
+    return _TokensPosGatherAddFn.apply(x, pos, ids_keep, ids_restore, B, L)
+
+
+class _TokensUnshuffleFn(Function):
+    """Decoder input without a class row: kept tokens back at their positions, the mask token elsewhere, + pos (a fixed
+    table).  The mask token's gradient is added into ``mask_token.grad`` (as _UnshuffleFn of the MAE backbone does)."""
+
+    @staticmethod
+    def forward(ctx, x, mask_token, pos, ids_keep, ids_restore, B):
+        ctx.ids = (ids_keep, ids_restore)
+        ctx.tok, ctx.B = mask_token, B
+        param_expect_grad(mask_token)
+        return ops.tokens_unshuffle(x, mask_token.detach().view(-1), pos.detach().view(-1, pos.shape[-1]), ids_restore,
+                                    B, ids_keep.shape[1])
+
+    @staticmethod
+    def backward(ctx, dout):
+        ids_keep, ids_restore = ctx.ids
+        tok = ctx.tok
+        if tok.grad is None:
+            tok.grad = torch.zeros_like(tok)
+        dx = ops.tokens_unshuffle_bwd(dout.contiguous(), ids_keep, ids_restore, tok.grad.view(-1), ctx.B)
+        param_grad_ready(tok)
+        return dx, None, None, None, None, None
+
+
+def tokens_unshuffle(x, mask_token, pos, ids_keep, ids_restore, B):
+    """x [B*K, D] -> [B*L, D]."""
+    return _TokensUnshuffleFn.apply(x, mask_token, pos, ids_keep, ids_restore, B)
+
+
+class _TokensMAELossFn(Function):
+    """MAE's masked-patch loss on prediction rows [B*L, p*p*3] without class rows (loss/mae.py has the form with)."""
+
+    @staticmethod
+    def forward(ctx, pred, imgs, mask, p, norm_pix, denom):
+        ctx.save_for_backward(pred, imgs, mask)
+        ctx.args = (p, norm_pix, denom)
+        return ops.tokens_mae_loss_fwd(imgs, pred, mask, p, norm_pix, denom)
+
+    @staticmethod
+    def backward(ctx, gloss):
+        pred, imgs, mask = ctx.saved_tensors
+        p, norm_pix, denom = ctx.args
+        return ops.tokens_mae_loss_bwd(imgs, pred, mask, gloss.contiguous().float(), p, norm_pix, denom), None, None, \
+            None, None, None
+
+
+def tokens_masked_patch_loss(pred_rows, imgs, mask, patch_size, norm_pix_loss, denom):
+    """pred_rows fp32 [B*L, p*p*3], imgs fp32 [B, 3, H, W], mask [B, L] (1 = removed), denom = mask.sum() as the host
+    knows it."""
+    return _TokensMAELossFn.apply(pred_rows, imgs.contiguous().float(), mask, int(patch_size), bool(norm_pix_loss),
+                                  float(denom))
+
+
 class _PatchConvFn(Function):
     """Biased kernel = stride convolution over NHWC on the implicit-GEMM kernel: the bias is the epilogue's ``shift``,
     the data gradient goes through plan.dgrad_plan (stride 2 splits into residue classes), dW through wgrad_desc and

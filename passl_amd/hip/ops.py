@@ -1132,6 +1132,140 @@ def dwconv7_bwd_weight_into(x, dy, dw, dbias):
     return dw, dbias
 
 
+# ------------------------------------------------------------------ ConvMAE (csrc/convmae.hip)
+def dwconv5_wgrad_ws_floats(N, H, W, Cc):
+    """include/passl_hip.h: PASSL_DWCONV5_WGRAD_WS_FLOATS."""
+    return min(N * -(-H // 8) * -(-W // 16), 512) * 26 * Cc
+
+
+def tokens_unshuffle_bwd_ws_floats(D):
+    """include/passl_hip.h: PASSL_TOKENS_UNSHUFFLE_BWD_WS_FLOATS."""
+    return 1024 * D
+
+
+def _mask_grid(mask, grid):
+    """(Hm, Wm) for the entry points: the grid of a given mask table, zeros (not read) without one."""
+    if mask is None:
+        return 0, 0
+    Hm, Wm = grid
+    if mask.dtype != torch.float32 or mask.shape[-1] != Hm * Wm:
+        raise ValueError('mask %s %s does not hold an fp32 %d x %d grid' % (tuple(mask.shape), mask.dtype, Hm, Wm))
+    return Hm, Wm
+
+
+def dwconv5_masked_fwd(x, w, bias, mask=None, grid=None):
+    """Depthwise 5x5, padding 2, of keep * x: x NHWC [N, H, W, C]; w fp32 [C, 1, 5, 5] (the parameter as it lies), bias
+    fp32 [C]; mask fp32 [N, Hm * Wm] (1 = removed, grid = (Hm, Wm)) or None."""
+    N, H, W, Cc = x.shape
+    Hm, Wm = _mask_grid(mask, grid)
+    y = torch.empty_like(x)
+    L.check(_lib().passl_hip_dwconv5_masked_fwd(L.ptr(x), L.ptr(w), L.ptr(bias), L.ptr(mask), L.ptr(y), N, H, W, Cc,
+                                                Hm, Wm, L.dt(x), L.stream()), 'dwconv5_masked_fwd')
+    return y
+
+
+def dwconv5_masked_bwd_data(dy, w, mask=None, grid=None):
+    """dx of dwconv5_masked_fwd: zero at the removed pixels."""
+    N, H, W, Cc = dy.shape
+    Hm, Wm = _mask_grid(mask, grid)
+    dx = torch.empty_like(dy)
+    L.check(_lib().passl_hip_dwconv5_masked_bwd_data(L.ptr(dy), L.ptr(w), L.ptr(mask), L.ptr(dx), N, H, W, Cc, Hm, Wm,
+                                                     L.dt(dy), L.stream()), 'dwconv5_masked_bwd_data')
+    return dx
+
+
+def dwconv5_masked_bwd_weight_into(x, dy, dw, dbias, mask=None, grid=None):
+    """dw [C, 1, 5, 5] and dbias [C] (fp32, WRITTEN) of dwconv5_masked_fwd."""
+    N, H, W, Cc = x.shape
+    Hm, Wm = _mask_grid(mask, grid)
+    ws = workspace.get(dwconv5_wgrad_ws_floats(N, H, W, Cc), x.device)
+    L.check(_lib().passl_hip_dwconv5_masked_bwd_weight(L.ptr(x), L.ptr(dy), L.ptr(mask), L.ptr(dw), L.ptr(dbias),
+                                                       L.ptr(ws), ws.numel(), N, H, W, Cc, Hm, Wm, L.dt(x), L.stream()),
+            'dwconv5_masked_bwd_weight')
+    return dw, dbias
+
+
+def patch_gather_fwd(x, ids_keep, grid, p):
+    """x NHWC [B, Hm*p, Wm*p, C], ids_keep int32 [B, K] -> the kept patches' GEMM rows [B*K, p*p*C], columns (ph, pw, c)."""
+    B, H, W, Cc = x.shape
+    Hm, Wm = grid
+    if H != Hm * p or W != Wm * p:
+        raise ValueError('patch_gather: a %d x %d map is not a %d x %d grid of %d x %d patches' % (H, W, Hm, Wm, p, p))
+    K = ids_keep.shape[1]
+    out = torch.empty(B * K, p * p * Cc, dtype=x.dtype, device=x.device)
+    L.check(_lib().passl_hip_patch_gather_fwd(L.ptr(x), L.ptr(ids_keep), L.ptr(out), B, K, Hm, Wm, p, Cc, L.dt(x),
+                                              L.stream()), 'patch_gather_fwd')
+    return out
+
+
+def patch_gather_bwd(dout, ids_restore, B, K, grid, p, Cc):
+    """dx NHWC [B, Hm*p, Wm*p, C] of patch_gather_fwd, fully written (zeros at the removed patches)."""
+    Hm, Wm = grid
+    dx = torch.empty(B, Hm * p, Wm * p, Cc, dtype=dout.dtype, device=dout.device)
+    L.check(_lib().passl_hip_patch_gather_bwd(L.ptr(dout), L.ptr(ids_restore), L.ptr(dx), B, K, Hm, Wm, p, Cc,
+                                              L.dt(dout), L.stream()), 'patch_gather_bwd')
+    return dx
+
+
+def tokens_pos_gather_add(x, pos, ids_keep, B, Ln, K):
+    """out[b, k] = x[b, k] + pos[ids_keep[b, k]]: x [B*K, D] (or [B, K, D]), pos fp32 [Ln, D]."""
+    D = x.shape[-1]
+    out = torch.empty_like(x)
+    L.check(_lib().passl_hip_tokens_pos_gather_add(L.ptr(x), L.ptr(pos), L.ptr(ids_keep), L.ptr(out), B, Ln, K, D,
+                                                   L.dt(x), L.stream()), 'tokens_pos_gather_add')
+    return out
+
+
+def tokens_pos_gather_add_bwd_into(dout, ids_restore, dpos, B, Ln, K):
+    """dpos fp32 [Ln, D] += the kept rows of dout, added over the images in ascending order."""
+    D = dout.shape[-1]
+    L.check(_lib().passl_hip_tokens_pos_gather_add_bwd(L.ptr(dout), L.ptr(ids_restore), L.ptr(dpos), B, Ln, K, D,
+                                                       L.dt(dout), L.stream()), 'tokens_pos_gather_add_bwd')
+    return dpos
+
+
+def tokens_unshuffle(x, mask_token, pos, ids_restore, B, K):
+    """Decoder input without a class row: x [B*K, D] -> [B*Ln, D]."""
+    D = x.shape[-1]
+    Ln = ids_restore.shape[1]
+    out = torch.empty(B * Ln, D, dtype=x.dtype, device=x.device)
+    L.check(_lib().passl_hip_tokens_unshuffle(L.ptr(x), L.ptr(mask_token), L.ptr(pos), L.ptr(ids_restore), L.ptr(out),
+                                              B, Ln, K, D, L.dt(x), L.stream()), 'tokens_unshuffle')
+    return out
+
+
+def tokens_unshuffle_bwd(dout, ids_keep, ids_restore, dmask_token, B):
+    """dx [B*K, D]; dmask_token (fp32 [D]) += the removed positions' rows of dout."""
+    D = dout.shape[-1]
+    Ln, K = ids_restore.shape[1], ids_keep.shape[1]
+    dx = torch.empty(B * K, D, dtype=dout.dtype, device=dout.device)
+    ws = workspace.get(tokens_unshuffle_bwd_ws_floats(D), dout.device)
+    L.check(_lib().passl_hip_tokens_unshuffle_bwd(L.ptr(dout), L.ptr(ids_keep), L.ptr(ids_restore), L.ptr(dx),
+                                                  L.ptr(dmask_token), B, Ln, K, D, L.dt(dout), L.ptr(ws), ws.numel(),
+                                                  L.stream()), 'tokens_unshuffle_bwd')
+    return dx
+
+
+def tokens_mae_loss_fwd(img, pred, mask, p, norm_pix, denom):
+    """The masked-patch loss on pred fp32 [B*L, p*p*C] (no class rows)."""
+    B, Cc, H, W = img.shape
+    loss = torch.empty(1, dtype=torch.float32, device=img.device)
+    ws = workspace.get(B * (H // p) * (W // p), img.device)
+    L.check(_lib().passl_hip_tokens_mae_loss_fwd(L.ptr(img), L.ptr(pred), L.ptr(mask), L.ptr(loss), B, Cc, H, W, p,
+                                                 1 if norm_pix else 0, denom, L.ptr(ws), ws.numel(), L.stream()),
+            'tokens_mae_loss_fwd')
+    return loss
+
+
+def tokens_mae_loss_bwd(img, pred, mask, gscale, p, norm_pix, denom):
+    B, Cc, H, W = img.shape
+    dpred = torch.empty_like(pred)
+    L.check(_lib().passl_hip_tokens_mae_loss_bwd(L.ptr(img), L.ptr(pred), L.ptr(mask), L.ptr(gscale), L.ptr(dpred), B,
+                                                 Cc, H, W, p, 1 if norm_pix else 0, denom, L.stream()),
+            'tokens_mae_loss_bwd')
+    return dpred
+
+
 def layer_scale_add_fwd(branch, residual, gamma, keep_row, keep_prob, B, T):
     """residual + keep_row[b] * ((gamma * branch) / keep_prob) over rows [B*T, C]; keep_row None: rate 0 / evaluation."""
     Cc = branch.shape[-1]

@@ -4,3 +4,4 @@ from .resnetsimclr import ResNetsimclr, ResNetCifar
 from .mae import MAE, MAE_ViT
 from .vision_transformer import VisionTransformer
 from .clip import CLIP
+from .convmae import ConvMAE            # (last: imports passl_amd.models.convmae, which imports this package's builder)
