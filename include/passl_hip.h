@@ -575,20 +575,23 @@ int passl_hip_attention_bwd(const void* qkv, const void* out, const void* dout, 
 int passl_hip_mae_mask(const float* noise, int B, int L, int len_keep, int32_t* ids_keep,
                        int32_t* ids_restore, float* mask, passl_stream_t stream);
 /* encoder input (mae.py:494-503): out[b,0] = cls + pos[0]; out[b,1+k] = x[b,ids_keep[b,k]] +
- * pos[1+ids_keep[b,k]];  x [B,L,D], pos [L+1,D], out [B,K+1,D]. */
+ * pos[1+ids_keep[b,k]];  x [B,L,D], pos [L+1,D], out [B,K+1,D].  D a multiple of 8; x, cls, pos and out 16-byte
+ * aligned (PASSL_EINVAL otherwise, before any launch). */
 int passl_hip_mae_gather(const void* x, const float* cls, const float* pos, const int32_t* ids_keep,
                          void* out, int B, int L, int K, int D, int dtype, passl_stream_t stream);
 /* its backward: dx [B,L,D] fully written (zeros at masked patches), dcls += sum_b dout[b,0] (images added in
- * a fixed order). */
+ * a fixed order).  dout and dx 16-byte aligned (PASSL_EINVAL otherwise, before any launch). */
 int passl_hip_mae_gather_bwd(const void* dout, const int32_t* ids_restore, void* dx, float* dcls,
                              int B, int L, int K, int D, int dtype, passl_stream_t stream);
 /* decoder input (mae.py:516-527): out[b,0] = x[b,0] + pos[0]; out[b,1+l] = (r = ids_restore[b,l]) < K
- * ? x[b,1+r] : mask_token, + pos[1+l];  x [B,K+1,D], out [B,L+1,D]. */
+ * ? x[b,1+r] : mask_token, + pos[1+l];  x [B,K+1,D], out [B,L+1,D].  x, mask_token, pos and out 16-byte aligned
+ * (PASSL_EINVAL otherwise, before any launch). */
 int passl_hip_mae_unshuffle(const void* x, const float* mask_token, const float* pos,
                             const int32_t* ids_restore, void* out, int B, int L, int K, int D,
                             int dtype, passl_stream_t stream);
 /* its backward: dx [B,K+1,D] fully written, dmask_token += sum over masked positions (token-block slabs in
- * `ws`, >= 1024 * D floats, added in order: no atomics). */
+ * `ws`, >= 1024 * D floats, added in order: no atomics).  dout, dx, dmask_token and ws 16-byte aligned (PASSL_EINVAL
+ * otherwise, before any launch). */
 int passl_hip_mae_unshuffle_bwd(const void* dout, const int32_t* ids_keep, const int32_t* ids_restore,
                                 void* dx, float* dmask_token, int B, int L, int K, int D, int dtype,
                                 float* ws, int64_t ws_floats, passl_stream_t stream);

@@ -79,6 +79,10 @@ __global__ void __launch_bounds__(kThreads) embed_fwd_kernel(const int64_t* __re
 //                                 per-(position, image-slab) column sums of dout into the dpos slabs
 //   pass 3  embed_flush_kernel    dE[tok] += acc[tok] * 2^-(61-e) for touched tokens; acc and touched are cleared
 // acc / touched must be zero on entry and are zero again on return (a persistent workspace of the caller).
+// A non-finite gradient is not propagated into dE: fmaxf keeps a NaN out of amax and its fixed-point conversion is
+// undefined.  One run on an MI355X with a single NaN in dout (tests/test_token_numerics_gpu.py): dpos[t][c] came back
+// NaN, row text[b][t] of dE came back finite, column c holding the sum of its other addends (the NaN counted as 0),
+// every other row and the workspace contract unaffected.
 template <typename T>
 __global__ void __launch_bounds__(kThreads) embed_absmax_kernel(const T* __restrict__ dout, int64_t nchunks,
                                                                 uint32_t* __restrict__ amax) {

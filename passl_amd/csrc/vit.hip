@@ -672,7 +672,8 @@ extern "C" int passl_hip_mae_mask(const float* noise, int B, int L, int len_keep
 extern "C" int passl_hip_mae_gather(const void* x, const float* cls, const float* pos,
                                     const int32_t* ids_keep, void* out, int B, int L, int K, int D,
                                     int dtype, passl_stream_t stream) {
-  if (!x || !cls || !pos || !ids_keep || !out || B <= 0 || L <= 0 || K <= 0 || K > L || D <= 0 || (D & 7))
+  if (!x || !cls || !pos || !ids_keep || !out || B <= 0 || L <= 0 || K <= 0 || K > L || D <= 0 || (D & 7) ||
+      !aligned16(x) || !aligned16(cls) || !aligned16(pos) || !aligned16(out))
     return PASSL_EINVAL;
   PASSL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(mae_gather_kernel<T>, dim3(grid_for((int64_t)B * (K + 1) * (D >> 3))),
                                                  dim3(kThreads), 0, as_stream(stream),
@@ -685,7 +686,8 @@ extern "C" int passl_hip_mae_gather(const void* x, const float* cls, const float
 extern "C" int passl_hip_mae_gather_bwd(const void* dout, const int32_t* ids_restore, void* dx,
                                         float* dcls, int B, int L, int K, int D, int dtype,
                                         passl_stream_t stream) {
-  if (!dout || !ids_restore || !dx || !dcls || B <= 0 || L <= 0 || K <= 0 || K > L || D <= 0 || (D & 7))
+  if (!dout || !ids_restore || !dx || !dcls || B <= 0 || L <= 0 || K <= 0 || K > L || D <= 0 || (D & 7) ||
+      !aligned16(dout) || !aligned16(dx))
     return PASSL_EINVAL;
   PASSL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(mae_gather_bwd_kernel<T>,
                                                  dim3(grid_for((int64_t)B * L * (D >> 3))), dim3(kThreads), 0,
@@ -701,7 +703,7 @@ extern "C" int passl_hip_mae_unshuffle(const void* x, const float* mask_token, c
                                        const int32_t* ids_restore, void* out, int B, int L, int K,
                                        int D, int dtype, passl_stream_t stream) {
   if (!x || !mask_token || !pos || !ids_restore || !out || B <= 0 || L <= 0 || K <= 0 || K > L ||
-      D <= 0 || (D & 7))
+      D <= 0 || (D & 7) || !aligned16(x) || !aligned16(mask_token) || !aligned16(pos) || !aligned16(out))
     return PASSL_EINVAL;
   PASSL_DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(mae_unshuffle_kernel<T>,
                                                  dim3(grid_for((int64_t)B * (L + 1) * (D >> 3))), dim3(kThreads), 0,
@@ -720,7 +722,7 @@ extern "C" int passl_hip_mae_unshuffle_bwd(const void* dout, const int32_t* ids_
                                            int B, int L, int K, int D, int dtype, float* ws,
                                            int64_t ws_floats, passl_stream_t stream) {
   if (!dout || !ids_keep || !ids_restore || !dx || !dmask_token || !ws || B <= 0 || L <= 0 || K <= 0 ||
-      K > L || D <= 0 || (D & 7) || !aligned16(ws) || !aligned16(dmask_token))
+      K > L || D <= 0 || (D & 7) || !aligned16(ws) || !aligned16(dmask_token) || !aligned16(dout) || !aligned16(dx))
     return PASSL_EINVAL;
   const int64_t ntok = (int64_t)B * (L + 1);
   int slabs = (int)((ntok + 127) / 128);
