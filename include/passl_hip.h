@@ -1021,6 +1021,66 @@ int passl_hip_prefix_tokens_bwd(const void* dout, void* dx, float* dprefix0, flo
  * b == NULL: out = a / 2, the gradient both heads receive.  n > 0 and a, out non-NULL (PASSL_EINVAL otherwise). */
 int passl_hip_mean2(const float* a, const float* b, float* out, int64_t n, passl_stream_t stream);
 
+/* ---------------------------------------------------------------- CAE pre-training (csrc/cross_attention.hip, cae.hip)
+ * Reference: passl/models/cae.py, tasks/ssl/cae/engine_pretrain.py. */
+
+/* Cross-attention with separate operands and lengths (CAECrossAttention.forward, cae.py:244-257):
+ *   out = softmax(q k^T scale) v  per (image, head),
+ * q, out, dout, dq [B,Tq,H,DH]; k, v, dk, dv [B,Tk,H,DH], all contiguous in `dtype`; lse fp32 [B,H,Tq].  dq, dk and dv are
+ * three tensors and are fully written.  The kernels are those of passl_hip_attention_tiled_fwd / _bwd with the loop
+ * bounds Tq on the query side and Tk on the key side: a workgroup owns a block of query rows (dK / dV sweep: key columns)
+ * of one (image, head) and streams K and V (Q and dO) through LDS 64 rows at a time; fp32 online softmax; a padding key
+ * is not a key; P is recomputed from lse in the backward, delta_i = dO_i . O_i.  No atomics, no scratch, no workspace: two
+ * launches give the same bits, and with Tq = Tk and q, k, v the slices of one qkv the results have the bits of
+ * passl_hip_attention_tiled_fwd / _bwd.
+ * Operand routing is passl_hip_attention_tiled_fwd's: aligned bf16 takes bf16 MFMA; fp32, and bf16 with some pointer off
+ * 16-byte alignment, take exact-fp32 MFMA.
+ * Accepted: 1 <= Tq <= 1024, 1 <= Tk <= 1024, DH in {32, 64}, B and H positive (PASSL_EUNSUPPORTED otherwise, and for an
+ * unknown dtype); a NULL pointer is PASSL_EINVAL.  Nothing is launched unless PASSL_OK is returned. */
+int passl_hip_cross_attention_fwd(const void* q, const void* k, const void* v, void* out, float* lse, int B, int Tq,
+                                  int Tk, int H, int DH, float scale, int dtype, passl_stream_t stream);
+int passl_hip_cross_attention_bwd(const void* q, const void* k, const void* v, const void* out, const void* dout,
+                                  const float* lse, void* dq, void* dk, void* dv, int B, int Tq, int Tk, int H, int DH,
+                                  float scale, int dtype, passl_stream_t stream);
+/* The operands of the latent regressor (cae.py:440-444, 811-815, 1009-1015) from the visible latents xu [B,u0+Nu,C], read
+ * from row u0 of every image (u0 = 1 skips the encoder's class row, cae.py:1017, without a copy), the masked rows
+ * xm [B,Nm,C] (`dtype`), the fixed position table pos fp32 [1 + L, C] (row 0 is the class token's) and the
+ * index tables ids_vis int32 [B,Nu], ids_msk int32 [B,Nm] of patch numbers in [0, L):
+ *   q_in [B,Nm,C]      = xm + pos[1 + ids_msk]
+ *   v_in [B,Nu+Nm,C]   = concat(xu, xm)
+ *   k_in [B,Nu+Nm,C]   = v_in + concat(pos[1 + ids_vis], pos[1 + ids_msk])
+ * Any output may be NULL (not all three); with k_in = v_in = NULL only the masked rows are visited and xu, ids_vis are
+ * not read: the decoder's x_masked + pos_embed_masked (cae.py:823).  Sums in fp32, one rounding at the store; an index
+ * outside [0, L) is clamped.  One streaming launch, no expanded position tensor and no concat copy.
+ * The backward writes dxm = dq_in + dk_in[:, Nu:] + dv_in[:, Nu:] and dxu = dk_in[:, :Nu] + dv_in[:, :Nu] fully (fp32
+ * sums in that order, no accumulation; a NULL gradient counts as zero; dxu may be NULL: only dxm is formed).  dxu is
+ * [B,u0+Nu,C] and its first u0 rows of every image are written as zeros.  The table is fixed: there is no dpos.
+ * C % 8 == 0, every pointer 16-byte aligned, u0 >= 0, Nu >= 0, Nm > 0, dxu NULL when Nu == 0 (PASSL_EINVAL otherwise). */
+int passl_hip_cae_tokens_assemble(const void* xu, const void* xm, const float* pos, const int32_t* ids_vis,
+                                  const int32_t* ids_msk, void* q_in, void* k_in, void* v_in, int B, int u0, int Nu,
+                                  int Nm, int L, int C, int dtype, passl_stream_t stream);
+int passl_hip_cae_tokens_assemble_bwd(const void* dq_in, const void* dk_in, const void* dv_in, void* dxu, void* dxm,
+                                      int B, int u0, int Nu, int Nm, int C, int dtype, passl_stream_t stream);
+/* The index tables of a 0/1 fp32 mask [B, L] (1 = masked) with L - Nu ones per image, in ascending patch order — the
+ * order of the reference's boolean indexing x[~bool_masked_pos] / x[bool_masked_pos] (cae.py:662, 1011-1015):
+ *   ids_vis int32 [B, Nu]    the visible patches,      ids_msk int32 [B, L - Nu]   the masked patches,
+ *   rank int32 [B, L]        a visible patch's place among the visible ones, Nu + its place among the masked ones for a
+ *                            masked patch (passl_hip_mae_gather_bwd's ids_restore for the gather on ids_vis).
+ * One launch, one wave per image: passl_hip_mae_mask with the mask as its noise gives ids_vis and rank, this entry the
+ * masked side as well.  A mask with another count of ones writes nothing outside the tables and fills what is left of
+ * them with 0.  0 < Nu < L (PASSL_EINVAL otherwise). */
+int passl_hip_cae_mask_ids(const float* mask, int32_t* ids_vis, int32_t* ids_msk, int32_t* rank, int B, int L, int Nu,
+                           passl_stream_t stream);
+/* F.mse_loss(pred.float(), target.float(), 'mean') (engine_pretrain.py:29-31): pred [B,Tm,C], target [B,Tm+t0,C] read
+ * from row t0 of every image (t0 = 1 drops the teacher's class row, cae.py:984, without a copy), both in `dtype`.
+ * loss[0] = sum (pred - target)^2 / (B Tm C): differences, squares and sums in fp32, one wave per row into ws (B Tm
+ * floats), the rows added in a fixed order.  The backward is dpred = gloss 2 (pred - target) / (B Tm C) in `dtype`
+ * (gloss: device scalar, NULL = 1); the target has no gradient.  C % 8 == 0, pointers 16-byte aligned. */
+int passl_hip_mse_fwd(const void* pred, const void* target, float* loss, int B, int Tm, int t0, int C, int dtype,
+                      float* ws, int64_t ws_floats, passl_stream_t stream);
+int passl_hip_mse_bwd(const void* pred, const void* target, const float* gloss, void* dpred, int B, int Tm, int t0, int C,
+                      int dtype, passl_stream_t stream);
+
 /* ---------------------------------------------------------------- mixup / cutmix and soft-target cross-entropy
  * Reference: class Mixup, passl_v110/datasets/preprocess/mixup.py:108-276 (the reference mixes on the host, in numpy or
  * through the framework's CPU tensors); SoftTargetCrossEntropy, tasks/ssl/mae/util/loss.py:44-47. */

@@ -12,7 +12,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT_DIR = os.path.join(os.path.dirname(HERE), 'lib')
 LIB = os.path.join(OUT_DIR, 'libpassl_hip.so')
-SOURCES = ['runtime.hip', 'plan.hip', 'flat.hip', 'layout_pool.hip', 'stem_pool.hip', 'bn.hip', 'head.hip', 'ntxent.hip', 'vit.hip', 'adan.hip', 'drop_path.hip', 'dwconv.hip', 'convmae.hip', 'dropout.hip', 'mixup.hip', 'random_erasing.hip', 'crop_resize.hip', 'view_aug.hip', 'attention.hip', 'attention_bf16.hip', 'attention_tiled.hip', 'window_attention.hip', 'cait_attention.hip', 'deit_tokens.hip', 'tome.hip', 'clip.hip', 'clas.hip',
+SOURCES = ['runtime.hip', 'plan.hip', 'flat.hip', 'layout_pool.hip', 'stem_pool.hip', 'bn.hip', 'head.hip', 'ntxent.hip', 'vit.hip', 'adan.hip', 'drop_path.hip', 'dwconv.hip', 'convmae.hip', 'dropout.hip', 'mixup.hip', 'random_erasing.hip', 'crop_resize.hip', 'view_aug.hip', 'attention.hip', 'attention_bf16.hip', 'attention_tiled.hip', 'cross_attention.hip', 'cae.hip', 'window_attention.hip', 'cait_attention.hip', 'deit_tokens.hip', 'tome.hip', 'clip.hip', 'clas.hip',
            'conv_igemm.hip', 'conv3x3_wave.hip', 'conv_igemm_ring.hip', 'conv_igemm_8p.hip', 'conv_stem.hip', 'conv_wgrad.hip']
 HEADERS = ['common.h', 'bn_chunk.h', 'philox.h', 'options.h', 'plan.h', 'prof.h', 'igemm_epi.h', 'igemm_dma.h', 'halo_geom.h', 'wgrad_halo_geom.h', 'conv_wgrad_halo.inc', 'view_aug_pixel.h', 'eltwise.h', 'gelu_op.h', 'terms_finish.h', 'attention_core.h', 'attention_ops_f32.h', 'attention_ops_bf16.h', os.path.join('..', '..', 'include', 'passl_hip.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC',

@@ -125,6 +125,74 @@ class SyntheticRawTwoView(object):
 
 
 @DATASETS.register()
+class SyntheticMaskedTokens(object):
+    """(image, mask, labels) batches of CAE pre-training under the reference's ``--target_mode random`` contract
+    (tasks/ssl/cae/engine_pretrain.py:77-78, 127-128: the visual token ids come with the batch; the DALL-E tokenizer is
+    not built): image ~ N(0,1) fp32 [3,S,S], token ids int64 [L] in [0, vocab), L = (S / patch)^2.  Images and token ids
+    are what the loader keeps resident (``make_batch``); the masks are drawn on the host for EVERY batch that is handed
+    out (``per_iteration``: preprocess.masking, 'block' with ``num_mask_patches`` ones per image or 'random' with
+    ``ratio_masking_patches``), moved to the device, and the loader does the label gather: a step receives
+    (images [B,3,S,S], mask fp32 [B,L] with 1 = masked, labels int64 [B Nm] = input_ids[bool_masked_pos]) and reads
+    nothing back.
+
+    The generators draw from ``random`` / ``np.random`` as the reference's do; the dataset keeps a stream of its own for
+    both, seeded by ``seed``, and swaps it in around a draw: the process-wide generators are left as they were."""
+
+    def __init__(self, num_samples=1281167, image_size=224, patch_size=16, vocab_size=8192, mask_generator='block',
+                 num_mask_patches=75, min_mask_patches_per_block=16, max_mask_patches_per_block=None,
+                 ratio_masking_patches=None, seed=1234, num_batches_cached=1, **ignored):
+        import random
+
+        import numpy as np
+
+        from .preprocess.masking import MaskingGenerator, RandomMaskingGenerator
+        self.num_samples, self.image_size, self.patch_size = int(num_samples), int(image_size), int(patch_size)
+        self.vocab_size, self.seed, self.num_batches_cached = int(vocab_size), int(seed), int(num_batches_cached)
+        self.grid = self.image_size // self.patch_size
+        if mask_generator == 'block':
+            self.generator = MaskingGenerator((self.grid, self.grid), num_masking_patches=int(num_mask_patches),
+                                              max_num_patches=max_mask_patches_per_block,
+                                              min_num_patches=int(min_mask_patches_per_block))
+        elif mask_generator == 'random':
+            self.generator = RandomMaskingGenerator((self.grid, self.grid), float(ratio_masking_patches))
+        else:
+            raise NotImplementedError("mask_generator %r (known: 'block', 'random')" % (mask_generator,))
+        self.num_masked = self.generator.num_masking_patches
+        self._streams = (random.Random(self.seed).getstate(), np.random.RandomState(self.seed).get_state())
+
+    def __len__(self):
+        return self.num_samples
+
+    def make_batch(self, gen, batch_size):
+        """The resident part: (images, token ids [B, L])."""
+        s, L = self.image_size, self.grid * self.grid
+        return (torch.randn(batch_size, 3, s, s, generator=gen),
+                torch.randint(0, self.vocab_size, (batch_size, L), generator=gen))
+
+    def draw_masks(self, batch_size):
+        """fp32 [B, L] on the host, from the dataset's own stream of the two process-wide generators."""
+        import random
+
+        import numpy as np
+        outer = (random.getstate(), np.random.get_state())
+        random.setstate(self._streams[0])
+        np.random.set_state(self._streams[1])
+        try:
+            masks = np.stack([np.asarray(self.generator()).reshape(-1) for _ in range(batch_size)])
+            self._streams = (random.getstate(), np.random.get_state())
+        finally:
+            random.setstate(outer[0])
+            np.random.set_state(outer[1])
+        return torch.from_numpy(masks).float()
+
+    def per_iteration(self, batch):
+        """(images, ids) as cached -> (images, mask, labels) with a fresh mask (SyntheticLoader calls this per batch)."""
+        image, ids = batch
+        mask = self.draw_masks(image.shape[0]).to(ids.device)
+        return image, mask, ids[mask.bool()]
+
+
+@DATASETS.register()
 class ImageNet(object):
     def __init__(self, **kwargs):
         raise NotImplementedError(
@@ -201,6 +269,8 @@ class SyntheticLoader(object):
             b = self._cache[i % len(self._cache)]
             if self._tail and i == n - 1 and self._len > 0:
                 b = tuple(t[:self._tail] for t in b)
+            if hasattr(self.dataset, 'per_iteration'):       # what a dataset draws afresh for every batch handed out
+                b = self.dataset.per_iteration(b)
             if self.batch_transform is not None:
                 out = self.batch_transform(b[0])             # (a TwoViewsTransform hands out two tensors)
                 b = (out if isinstance(out, tuple) else (out,)) + tuple(b[1:])

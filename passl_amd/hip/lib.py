@@ -135,6 +135,13 @@ SIGNATURES = {
     'passl_hip_attention_bwd': (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_p]),
     'passl_hip_attention_tiled_fwd': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_p]),
     'passl_hip_attention_tiled_bwd': (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_p]),
+    'passl_hip_cross_attention_fwd': (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_p]),
+    'passl_hip_cross_attention_bwd': (c_i, [c_p] * 9 + [c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_p]),
+    'passl_hip_cae_tokens_assemble': (c_i, [c_p] * 8 + [c_i] * 7 + [c_p]),
+    'passl_hip_cae_tokens_assemble_bwd': (c_i, [c_p] * 5 + [c_i] * 6 + [c_p]),
+    'passl_hip_cae_mask_ids': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
+    'passl_hip_mse_fwd':(c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_l, c_p]),
+    'passl_hip_mse_bwd': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
     'passl_hip_window_attention_fwd': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_p]),
     'passl_hip_window_attention_bwd': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
                                              c_f, c_i, c_p]),

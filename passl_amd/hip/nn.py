@@ -1846,6 +1846,88 @@ def class_attention(q, k, v, B, T, H, DH, scale):
     return _ClassAttentionFn.apply(q, k, v, B, T, H, DH, float(scale))
 
 
+class _CrossAttentionFn(Function):
+    """CAE's cross-attention (csrc/cross_attention.hip): Tq queries against Tk keys, q / k / v three tensors."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, B, Tq, Tk, H, DH, scale):
+        _need_contiguous('cross_attention', q=q, k=k, v=v)
+        out, lse = ops.cross_attention_fwd(q, k, v, B, Tq, Tk, H, DH, scale)
+        ctx.save_for_backward(q, k, v, out, lse)
+        ctx.dims = (B, Tq, Tk, H, DH, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, lse = ctx.saved_tensors
+        return ops.cross_attention_bwd(q, k, v, out, dout.contiguous(), lse, *ctx.dims) + (None,) * 6
+
+
+def cross_attention(q, k, v, B, Tq, Tk, H, DH, scale):
+    """q: rows [B*Tq, H*DH]; k, v: rows [B*Tk, H*DH] -> [B*Tq, H*DH]."""
+    return _CrossAttentionFn.apply(q, k, v, B, Tq, Tk, H, DH, float(scale))
+
+
+class _CAETokensAssembleFn(Function):
+    """The regressor's operands from the visible and the masked rows and the fixed position table (csrc/cae.hip)."""
+
+    @staticmethod
+    def forward(ctx, xu, xm, pos, ids_vis, ids_msk, B, u0):
+        _need_contiguous('cae_tokens_assemble', xu=xu, xm=xm)
+        ctx.dims = (B, ids_vis.shape[1], ids_msk.shape[1], u0)
+        return ops.cae_tokens_assemble(xu, xm, pos, ids_vis, ids_msk, B, u0=u0)
+
+    @staticmethod
+    def backward(ctx, dq_in, dk_in, dv_in):
+        g = [None if t is None else t.contiguous() for t in (dq_in, dk_in, dv_in)]
+        return ops.cae_tokens_assemble_bwd(g[0], g[1], g[2], *ctx.dims) + (None,) * 5
+
+
+def cae_tokens_assemble(xu, xm, pos, ids_vis, ids_msk, B, u0=0):
+    """xu [B*(u0+Nu), C] (the first u0 rows of every image are skipped), xm [B*Nm, C] ->
+    (q_in [B*Nm, C], k_in [B*(Nu+Nm), C], v_in [B*(Nu+Nm), C])."""
+    return _CAETokensAssembleFn.apply(xu, xm, pos, ids_vis, ids_msk, B, u0)
+
+
+class _CAEPosAddFn(Function):
+    """x_masked + pos[1 + ids_msk]: the same entry with q_in only; the gradient passes through unchanged."""
+
+    @staticmethod
+    def forward(ctx, xm, pos, ids_msk, B):
+        _need_contiguous('cae_pos_add', xm=xm)
+        return ops.cae_tokens_assemble(None, xm, pos, None, ids_msk, B, want_kv=False)[0]
+
+    @staticmethod
+    def backward(ctx, dy):
+        return dy, None, None, None
+
+
+def cae_pos_add(xm, pos, ids_msk, B):
+    return _CAEPosAddFn.apply(xm, pos, ids_msk, B)
+
+
+class _MSEFn(Function):
+    """F.mse_loss(pred.float(), target.float(), 'mean') with the target read from row t0 of every image; the target has
+    no gradient."""
+
+    @staticmethod
+    def forward(ctx, pred, target, B, Tm, t0):
+        _need_contiguous('mse_loss', pred=pred, target=target)
+        ctx.save_for_backward(pred, target)
+        ctx.dims = (B, Tm, t0)
+        return ops.mse_fwd(pred, target, B, Tm, t0)
+
+    @staticmethod
+    def backward(ctx, gloss):
+        pred, target = ctx.saved_tensors
+        return ops.mse_bwd(pred, target, gloss.contiguous().float(), *ctx.dims), None, None, None, None
+
+
+def mse_loss(pred, target, B, Tm, t0=0):
+    """pred rows [B*Tm, C], target rows [B*(Tm + t0), C] -> fp32 [1]."""
+    return _MSEFn.apply(pred, target.detach(), B, Tm, t0)
+
+
 class _PosAddFn(Function):
     """rows [B*L, C] + pos_embed [1, L, C] (cait.py:354).  Backward: dx is dout; dpos += its column sums over the batch,
     straight into pos.grad."""

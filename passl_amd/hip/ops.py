@@ -803,6 +803,82 @@ def attention_tiled_bwd(qkv, out, dout, lse, B, T, H, DH, scale):
     return dqkv
 
 
+# ------------------------------------------------------------------ CAE (csrc/cross_attention.hip, csrc/cae.hip)
+# the envelope of csrc/cross_attention.hip (check_shape): either length, same head dimensions
+CROSS_ATTENTION_MAX_TOKENS = 1024
+
+
+def cross_attention_fwd(q, k, v, B, Tq, Tk, H, DH, scale):
+    """q [B*Tq, H*DH], k and v [B*Tk, H*DH] -> out [B*Tq, H*DH], lse [B, H, Tq]."""
+    out = torch.empty(B * Tq, H * DH, dtype=q.dtype, device=q.device)
+    lse = torch.empty(B, H, Tq, dtype=torch.float32, device=q.device)
+    L.check(_lib().passl_hip_cross_attention_fwd(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), L.ptr(lse), B, Tq, Tk, H, DH,
+                                                 scale, L.dt(q), L.stream()), 'cross_attention_fwd')
+    return out, lse
+
+
+def cross_attention_bwd(q, k, v, out, dout, lse, B, Tq, Tk, H, DH, scale):
+    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    L.check(_lib().passl_hip_cross_attention_bwd(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), L.ptr(dout), L.ptr(lse),
+                                                 L.ptr(dq), L.ptr(dk), L.ptr(dv), B, Tq, Tk, H, DH, scale, L.dt(q),
+                                                 L.stream()), 'cross_attention_bwd')
+    return dq, dk, dv
+
+
+def cae_tokens_assemble(xu, xm, pos, ids_vis, ids_msk, B, want_q=True, want_kv=True, u0=0):
+    """xu [B*(u0 + Nu), C] (read from row u0 of every image) or None, xm [B*Nm, C], pos fp32 [1 + L, C], ids int32
+    [B, Nu] / [B, Nm] -> (q_in [B*Nm, C], k_in [B*(Nu + Nm), C], v_in likewise); what is not wanted is None."""
+    Nm, D = ids_msk.shape[1], xm.shape[-1]
+    Nu = ids_vis.shape[1] if (want_kv and ids_vis is not None) else 0
+    q_in = torch.empty(B * Nm, D, dtype=xm.dtype, device=xm.device) if want_q else None
+    k_in = torch.empty(B * (Nu + Nm), D, dtype=xm.dtype, device=xm.device) if want_kv else None
+    v_in = torch.empty_like(k_in) if want_kv else None
+    L.check(_lib().passl_hip_cae_tokens_assemble(L.ptr(xu if Nu else None), L.ptr(xm), L.ptr(pos),
+                                                 L.ptr(ids_vis if Nu else None), L.ptr(ids_msk), L.ptr(q_in),
+                                                 L.ptr(k_in), L.ptr(v_in), B, u0, Nu, Nm, pos.shape[0] - 1, D, L.dt(xm),
+                                                 L.stream()), 'cae_tokens_assemble')
+    return q_in, k_in, v_in
+
+
+def cae_tokens_assemble_bwd(dq_in, dk_in, dv_in, B, Nu, Nm, u0=0):
+    """-> (dxu [B*(u0 + Nu), C] with zero leading rows, or None when Nu = 0, dxm [B*Nm, C]); a gradient that is None
+    counts as zero."""
+    ref = next(t for t in (dq_in, dk_in, dv_in) if t is not None)
+    D = ref.shape[-1]
+    dxu = torch.empty(B * (u0 + Nu), D, dtype=ref.dtype, device=ref.device) if Nu else None
+    dxm = torch.empty(B * Nm, D, dtype=ref.dtype, device=ref.device)
+    L.check(_lib().passl_hip_cae_tokens_assemble_bwd(L.ptr(dq_in), L.ptr(dk_in), L.ptr(dv_in), L.ptr(dxu), L.ptr(dxm),
+                                                     B, u0, Nu, Nm, D, L.dt(ref), L.stream()), 'cae_tokens_assemble_bwd')
+    return dxu, dxm
+
+
+def cae_mask_ids(mask, Nu):
+    """mask fp32 [B, L] (1 = masked, L - Nu ones per image) -> (ids_vis [B, Nu], ids_msk [B, L - Nu], rank [B, L]) int32."""
+    B, Ln = mask.shape
+    ids_vis = torch.empty(B, Nu, dtype=torch.int32, device=mask.device)
+    ids_msk = torch.empty(B, Ln - Nu, dtype=torch.int32, device=mask.device)
+    rank = torch.empty(B, Ln, dtype=torch.int32, device=mask.device)
+    L.check(_lib().passl_hip_cae_mask_ids(L.ptr(mask), L.ptr(ids_vis), L.ptr(ids_msk), L.ptr(rank), B, Ln, Nu,
+                                          L.stream()), 'cae_mask_ids')
+    return ids_vis, ids_msk, rank
+
+
+def mse_fwd(pred, target, B, Tm, t0):
+    """pred [B*Tm, C], target [B*(Tm + t0), C] read from row t0 of every image -> loss fp32 [1]."""
+    loss = torch.empty(1, dtype=torch.float32, device=pred.device)
+    ws = workspace.get(B * Tm, pred.device)
+    L.check(_lib().passl_hip_mse_fwd(L.ptr(pred), L.ptr(target), L.ptr(loss), B, Tm, t0, pred.shape[-1], L.dt(pred),
+                                     L.ptr(ws), ws.numel(), L.stream()), 'mse_fwd')
+    return loss
+
+
+def mse_bwd(pred, target, gloss, B, Tm, t0):
+    dpred = torch.empty_like(pred)
+    L.check(_lib().passl_hip_mse_bwd(L.ptr(pred), L.ptr(target), L.ptr(gloss), L.ptr(dpred), B, Tm, t0, pred.shape[-1],
+                                     L.dt(pred), L.stream()), 'mse_bwd')
+    return dpred
+
+
 # ------------------------------------------------------------------ DeiT token assembly (csrc/deit_tokens.hip)
 def prefix_tokens_fwd(x, prefixes, pos, B, Ln):
     """x [B*L, C], prefixes: one or two fp32 [C] rows, pos fp32 [NP + L, C] -> [B*(NP + L), C] = [prefixes | x] + pos."""

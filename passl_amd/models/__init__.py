@@ -99,6 +99,8 @@ from .mae import (MaskedAutoencoderViT, mae_vit_base_patch16_dec512d8b, mae_vit_
                   mae_vit_huge_patch14_dec512d8b)
 from .convmae import *                                                # noqa: E402,F401,F403  (passl/models/__init__.py:32)
 from .convmae import ConvViT, MaskedAutoencoderConvViT                # noqa: E402,F401
+from .cae import *                                                    # noqa: E402,F401,F403  (passl/models/__init__.py:26)
+from .cae import CAEPretrain                                          # noqa: E402,F401
 from .simsiam import (SimSiamPretain, SimSiamLinearProbe, simsiam_resnet50_pretrain,      # noqa: E402,F401
                       simsiam_resnet50_linearprobe)
 
